@@ -13,6 +13,12 @@ cylindrical glass vial (two refracting interfaces per ray); --config 4 runs
 configs[3]: that vial around a scattering resin, 16 jittered rays per pixel;
 --config 5 --n 800 runs configs[4]: a square vial with an occluder mesh.
 
+A plain run sets up, warms up, times --steps iterations and prints the line.
+--full also measures the forward / adjoint call times, the visit count, the
+dense-gradient adjoint, the dominant kernel's roofline and the CPU baseline
+(null in a plain line).  --dump-outputs DIR writes the last timed iteration's
+pattern values and the loss of every iteration as DIR/<name>.npy.
+
 Multi-GPU: one process per GPU (torch.distributed.run), angles sharded in
 contiguous blocks, dose all-reduced over RCCL twice per iteration, L-BFGS
 dots all-reduced.  Rank 0 prints one JSON line.  `python bench.py --gpus N`
@@ -200,6 +206,26 @@ def make_roofline(args, N, A, world, prob, visits, rays, fwd_s, adj_s, kt=None):
             "counters_csrc_sha16": summ["csrc_sha16"], "csrc_sha16": here, **info}
 
 
+DUMP_MAX = 1 << 22  # entries of a dumped array: 16 MB of float32
+
+
+def dump_outputs(path, prob):
+    """--dump-outputs: what the last timed iteration left its caller, as <path>/<name>.npy.
+    patterns: the optimiser's pattern values after that iteration (float32; more than DUMP_MAX
+    entries: the entries at DUMP_MAX seeded positions, the same in every run); loss: the value
+    every iteration so far returned (float64).  The inputs are seeded (the start patterns above,
+    the analytic target), so two builds given the same arguments write comparable files."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    x = prob.patterns_local().reshape(-1)
+    if x.numel() > DUMP_MAX:
+        idx = torch.randint(x.numel(), (DUMP_MAX,), generator=torch.Generator().manual_seed(2))
+        x = x[idx.to(x.device)]
+    np.save(os.path.join(path, "patterns.npy"), x.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "loss.npy"), np.asarray(prob.loss_hist, dtype=np.float64))
+
+
 def launch_ranks(n):
     """`bench.py --gpus N` outside torch.distributed: run this same command as N ranks of a child
     torch.distributed.run (one process per GPU, 127.0.0.1 rendezvous on a free port) and exit with
@@ -219,8 +245,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); > 1 without WORLD_SIZE in the environment starts them itself; "
                          "under torch.distributed.run it must equal WORLD_SIZE")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed optimizer iterations (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the forward / adjoint call times (--breakdown iterations "
+                         "after the timed ones), the visit count, the dense-gradient adjoint, the dominant "
+                         "kernel's roofline with its live launch time, and the CPU baseline (--cpu-baseline); "
+                         "a plain run sets up, warms up, times --steps iterations and prints the line with "
+                         "those fields null")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed iteration left its caller as "
+                         "DIR/<name>.npy (float32 / float64): patterns.npy, the optimised pattern values of rank "
+                         "0 (beyond 2^22 entries a fixed, seeded sample of 2^22 of them), and loss.npy, the loss "
+                         "of every iteration so far (warmup, then timed)")
     ap.add_argument("--prewarm", type=float, default=1.0,
                     help="seconds of untimed forward projections before the warmup iterations (GPU and host "
                          "clocks of a fresh box ramp up; the optimiser state is not touched)")
@@ -237,8 +274,10 @@ def main():
     ap.add_argument("--zero-skip", action="store_true", help="skip rays whose pattern value is 0 (exact)")
     ap.add_argument("--stats", action="store_true", help="report float-fallback tiles per forward (syncs)")
     ap.add_argument("--breakdown", type=int, default=3,
-                    help="iterations after the timed ones whose forward / adjoint calls are timed (fwd_ms, adj_ms)")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+                    help="--full: iterations after the timed ones whose forward / adjoint calls are timed "
+                         "(fwd_ms, adj_ms)")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                    help="--full: time the CPU oracle on a sample of the workload (auto) or not (off)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--shard", choices=["auto", "angle", "slab"], default="auto",
                     help="multi-GPU partition: z-slabs of the film + DMD row bands (planar scenes, no dose "
@@ -259,6 +298,10 @@ def main():
                     help="start the ranks, form the process group, all-reduce one value and print the world "
                          "line without touching a GPU (tests of the launcher; use with --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # --emulate reports one shard's forward / adjoint times and visits: the measurements of --full
+    extras = args.full or bool(args.emulate)
 
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -320,11 +363,11 @@ def main():
     if prob.active_dense is not None:  # filter_radon: the compacted active set's entries
         prob.x0 = prob.x0[prob.active_dense].contiguous()
     del full
-    visits = prob.proj.count_visits(prob.spp, 0)
+    visits = prob.proj.count_visits(prob.spp, 0) if extras else None  # (a counting pass of its own)
     rays = prob.n_local * prob.spp
     log(f"[rank {rank}] setup {time.perf_counter() - t_setup:.1f}s, shard {prob.shard}: angles [{prob.a0},{prob.a1}), "
         f"slices [{prob.z0},{prob.z1}), rows [{prob.r0},{prob.r1}), "
-        f"visits/pass {visits:.3e}, rays {rays:.3e}")
+        + (f"visits/pass {visits:.3e}, " if extras else "") + f"rays {rays:.3e}")
 
     # HIP-event timing of the dominant kernels (forward / adjoint projection) on their launch stream
     fwd_ms, adj_ms = [], []
@@ -346,8 +389,9 @@ def main():
             return out
         return wrap
 
-    prob.proj.forward = timed(orig_fwd, fwd_ms)
-    prob.proj.adjoint = timed(orig_adj, adj_ms)
+    if extras:
+        prob.proj.forward = timed(orig_fwd, fwd_ms)
+        prob.proj.adjoint = timed(orig_adj, adj_ms)
     # overlapped angle shards render a forward as slice ranges (ShardedLoop.forward): one forward =
     # the ranges from slice 0 on, timed together
     fwd_slices, orig_slices = [], getattr(prob.proj, "forward_slices", None)
@@ -362,7 +406,7 @@ def main():
         fwd_slices.append((a[4] if len(a) > 4 else k.get("z0", 0), s, e))
         return out
 
-    if orig_slices is not None:
+    if extras and orig_slices is not None:
         prob.proj.forward_slices = timed_slices
 
     t_pre = time.perf_counter()
@@ -382,7 +426,8 @@ def main():
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
-    prob.proj.kernel_time(True)  # (dominant-kernel launch events from here on; no GPU work)
+    if extras:
+        prob.proj.kernel_time(True)  # (dominant-kernel launch events from here on; no GPU work)
     t0 = time.perf_counter()
     # step boundaries as events on the stream every launch goes to (the median of the steps)
     step_ev = [torch.cuda.Event(enable_timing=True)]
@@ -395,17 +440,20 @@ def main():
     if dist:
         dist.barrier()
     t1 = time.perf_counter()
-    kt = prob.proj.kernel_time(False)
+    kt = prob.proj.kernel_time(False) if extras else None
     elapsed = t1 - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, prob)
     # the forward / adjoint call times of the line (fwd_ms / adj_ms): events around each call, taken in
     # --breakdown iterations after the timed ones (an event record between two kernels idles the GPU
     # for a few microseconds: none in the timed steps beyond the step boundaries and the dominant
     # kernel's launch events)
-    state["on"] = True
-    for i in range(args.warmup + args.steps, args.warmup + args.steps + args.breakdown):
-        prob.iteration(i)
-    torch.cuda.synchronize()
-    state["on"] = False
+    if extras:
+        state["on"] = True
+        for i in range(args.warmup + args.steps, args.warmup + args.steps + args.breakdown):
+            prob.iteration(i)
+        torch.cuda.synchronize()
+        state["on"] = False
     fwd = [s.elapsed_time(e) for s, e in fwd_ms]
     if fwd_slices:  # per forward: the sum of its slice ranges' times
         for z0, s, e in fwd_slices:
@@ -422,8 +470,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-    log(f"[rank {rank}] {args.steps} iterations in {elapsed:.3f}s; fwd {fwd_avg * 1e3:.2f} ms, adj {adj_avg * 1e3:.2f} ms, "
-        f"last loss {prob.loss_hist[-1]:.6e}")
+    log(f"[rank {rank}] {args.steps} iterations in {elapsed:.3f}s; "
+        + (f"fwd {fwd_avg * 1e3:.2f} ms, adj {adj_avg * 1e3:.2f} ms, " if extras else "")
+        + f"last loss {prob.loss_hist[-1]:.6e}")
 
     if args.emulate:
         ew = int(args.emulate.split("/")[1])
@@ -467,7 +516,7 @@ def main():
     # where the thresholded loss's gradient is exactly 0 on most of the film and the adjoint skips those
     # partials and tiles (bit-identical); this is the same call with nothing to skip, untimed for `value`
     dense = None
-    if world == 1 and adj:
+    if extras and world == 1 and adj:
         gd = torch.empty(tuple(prob.proj.film_shape), device=dev).uniform_(
             -1.0, 1.0, generator=torch.Generator(device=dev).manual_seed(1))
         n_act = prob.x0.numel()
@@ -486,9 +535,9 @@ def main():
                  "note": "adjoint of a U[-1,1) gradient (no zero partials or tiles to skip), median of 5 calls; "
                          "ms_per_step_model = the median step with its adjoint replaced by this one"}
         del gd, ga
-    roofline = make_roofline(args, N, A, world, prob, visits, rays, fwd_avg, adj_avg, kt)
+    roofline = make_roofline(args, N, A, world, prob, visits, rays, fwd_avg, adj_avg, kt) if extras else None
     cpu = None
-    if args.cpu_baseline == "auto" and world == 1:
+    if extras and args.cpu_baseline == "auto" and world == 1:
         hi = host_info()
         log(f"cpu baseline ({hi['threads']} threads, and {hi['omp_threads']}; ~{args.cpu_seconds:.0f}s) ...")
         cpu = cpu_baseline(args.config, N, args.cpu_seconds, hi["threads"], hi["omp_threads"])
@@ -501,6 +550,7 @@ def main():
         "backend": (args.backend if dist else None),
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": elapsed / args.steps * 1e3,
         # the median of the timed steps (HIP events at the step boundaries) beside the mean
         "ms_per_step_median": step_med,
@@ -532,7 +582,9 @@ def main():
             "slab_bands": (len(prob.opt.pipeline.parts) if getattr(prob.opt, "pipeline", None) is not None else 1),
             "filter_radon": ({"active": prob.n_filtered, "of": prob.n_global} if prob.active_pixels is not None
                              else None),
-            "fwd_ms": fwd_avg * 1e3, "adj_ms": adj_avg * 1e3, "visits_per_pass": visits, "rays_per_pass": rays,
+            # --full: the call times of the --breakdown iterations and the counted visits (else null)
+            "fwd_ms": fwd_avg * 1e3 if extras else None, "adj_ms": adj_avg * 1e3 if extras else None,
+            "visits_per_pass": visits, "rays_per_pass": rays,
             "final_loss": prob.loss_hist[-1],
             # scattering: the last (line-search) forward's brick-bin chunks, how many the cache served
             "bins": prob.proj.bin_stats() if prob.proj.desc.albedo != 0.0 else None,

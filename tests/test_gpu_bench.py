@@ -27,7 +27,7 @@ def run(args, nproc=1, port=29641):
 
 
 def test_single_gpu_line():
-    r = run(["--res", "64", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"])
+    r = run(["--full", "--res", "64", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"])
     assert r["metric"] == "optimizer iterations/sec (fwd+adjoint), 64³ voxels × 64 angles"
     assert r["n_gpus"] == 1 and r["steps"] == 3 and r["value"] > 0
     assert r["cpu_baseline"]["kind"] == "port" and r["cpu_baseline"]["host"]["threads"] >= 1
@@ -43,6 +43,29 @@ def test_single_gpu_line():
     # counter summaries are committed for the BASELINE sizes only (profiles/r03/roofline_config<K>.json)
     assert set(r["roofline"]) >= {"bound", "achieved", "peak", "unit", "frac", "traffic"}
     assert r["roofline"]["frac"] is None and r["roofline"]["fwd_call_ms"] > 0
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the run times its steps and nothing else: the headline fields as ever, the
+    further measurements null; --dump-outputs writes the last timed iteration's patterns and the
+    loss of every iteration as float .npy files."""
+    import numpy as np
+    r = run(["--gpus", "1", "--res", "64", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")])
+    assert r["metric"] == "optimizer iterations/sec (fwd+adjoint), 64³ voxels × 64 angles"
+    assert r["unit"] == "it/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["steps"] == 3 and r["warmup"] == 2 and r["full"] is False and r["value"] > 0
+    assert r["ms_per_step"] == pytest.approx(1e3 / r["value"], rel=1e-9)
+    steps = r["ms_per_step_min_max"]
+    assert steps[0] <= r["ms_per_step_median"] <= steps[1]
+    assert r["cpu_baseline"] is None and r["roofline"] is None and r["dense_gradient"] is None
+    assert r["config"]["fwd_ms"] is None and r["config"]["visits_per_pass"] is None
+    assert sorted(os.listdir(tmp_path / "out")) == ["loss.npy", "patterns.npy"]
+    pat = np.load(tmp_path / "out" / "patterns.npy")
+    loss = np.load(tmp_path / "out" / "loss.npy")
+    assert pat.dtype == np.float32 and pat.shape == (64 ** 3,) and np.isfinite(pat).all() and pat.min() >= 0.0
+    assert pat.max() > 0.0
+    assert loss.dtype == np.float64 and loss.shape == (5,) and loss[-1] == r["config"]["final_loss"]
+    assert loss[-1] < loss[0]
 
 
 @pytest.mark.parametrize("shard,port", [("slab", 29651), ("angle", 29653)])

@@ -13,7 +13,7 @@ run() {  # name, bench args
   rm -rf $o/prof_$name
   echo "$name done" >&2
 }
-run config3 --config 3 --cpu-baseline off
-run config4 --config 4 --steps 2 --warmup 1 --cpu-baseline off
-run config5 --config 5 --n 800 --steps 2 --warmup 1 --cpu-baseline off
-timeout -k 10 400 python3 bench.py --config 5 --n 800 --steps 2 --warmup 1 --cpu-baseline off --filter-radon > $o/bench_config5_filter_radon.json 2> $o/bench_config5_filter_radon.err
+run config3 --full --config 3 --cpu-baseline off
+run config4 --full --config 4 --steps 2 --warmup 1 --cpu-baseline off
+run config5 --full --config 5 --n 800 --steps 2 --warmup 1 --cpu-baseline off
+timeout -k 10 400 python3 bench.py --full --config 5 --n 800 --steps 2 --warmup 1 --cpu-baseline off --filter-radon > $o/bench_config5_filter_radon.json 2> $o/bench_config5_filter_radon.err
