@@ -12,7 +12,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TVAM_LIB") or os.path.join(_HERE, "libtvam.so")  # TVAM_LIB: a variant build
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 TVAM_OK = 0
 TVAM_ERR_INVALID = -1
@@ -21,6 +21,8 @@ TVAM_ERR_HIP = -3
 TVAM_ERR_TOO_LARGE = -4
 
 PROJECTOR_COLLIMATED = 0
+PROJECTOR_TELECENTRIC = 1
+PROJECTOR_LENS = 2
 VIAL_INDEX_MATCHED = 0
 VIAL_CYLINDRICAL = 1
 VIAL_SQUARE = 2
@@ -36,6 +38,7 @@ FLAG_FWD_STATS = 2
 FLAG_NO_PLANAR = 4
 FLAG_RAY_FWD = 8
 FLAG_SCATTER_ATOMIC = 16
+FLAG_BIN_FIRST = 32
 LBFGS_WORK_DOUBLES = 2048 * 64
 
 
@@ -89,6 +92,8 @@ class TvamDesc(ctypes.Structure):
         ("reserved0", ctypes.c_int32),
         ("active_base", ctypes.c_int64),
         ("active_total", ctypes.c_int64),
+        ("aperture_radius", ctypes.c_float),
+        ("focus_distance", ctypes.c_float),
     ]
 
     def copy(self) -> "TvamDesc":
@@ -157,6 +162,7 @@ EXPORTS = {
     "tvam_compute_volume": (ctypes.c_int, [_P, ctypes.c_uint32, _P, _P]),
     "tvam_plan_set_volumes": (ctypes.c_int, [_P, _P]),
     "tvam_radon": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _P, _P]),
+    "tvam_plan_rays": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_count_visits": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
     "tvam_plan_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),
     "tvam_discretize": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P, _P]),

@@ -1,0 +1,337 @@
+// Telecentric and lens projectors (projector.py:199-296): projector rays with a finite
+// etendue.  Every ray starts on the aperture disk and passes its pixel's point of the focus
+// plane, so its first medium segment is a 3-D ray: it leaves its z-slice, and none of the
+// planar / tile kernels (d.z = 0) applies.  The pieces are the scattered segments' own
+// (tvam_seg3d.h, tvam_bricks.h): the open tube's 3-D hit, the 3-D DDA and the brick bins.
+//
+//   cn_ray            sampler draws (common.py:92-108: position next_2d if jittered, time
+//                     next_1d under sample_time, aperture next_2d), get_ray of the plan's
+//                     projector, CircularMotion's to_world (motion.py:26-36), the medium
+//                     segment behind the index-matched vial (volume.py:191-216, :268)
+//   tvam_cone_kernel  one thread per (ray, sample) marching cn_dda (the oracle's or_dda op for
+//                     op): forward with global float atomics, adjoint as a gather (a plain
+//                     store per active entry when spp == 1), visit count
+//   tvam_cone_emit_kernel   one brick-bin record per ray for tvam_scatter_binned (the binned
+//                     forward: bin fill, sort, tvam_bin_march_kernel and the bin cache)
+//   tvam_cone_export_kernel the rays themselves (tvam_plan_rays)
+#include "tvam_internal.h"
+
+#include <algorithm>
+
+#include "tvam_seg3d.h"
+
+namespace {
+
+struct ConeRay {
+    float o[3], d[3];  // world-space projector ray
+    float o2[3];       // medium segment (o2, d, [0, maxt])
+    float maxt;
+};
+
+// Mitsuba warp::square_to_uniform_disk_concentric (Shirley & Chiu), restated
+__device__ __forceinline__ void cn_disk(float u1, float u2, float& x, float& y) {
+    const float sx = 2.0f * u1 - 1.0f, sy = 2.0f * u2 - 1.0f;
+    const bool q = fabsf(sx) < fabsf(sy);
+    const float r = q ? sy : sx, rp = q ? sx : sy;
+    float phi = 0.78539816339744830962f * rp / r;
+    if (q) phi = 1.57079632679489661923f - phi;
+    if (sx == 0.0f && sy == 0.0f) phi = 0.0f;
+    x = r * cosf(phi);
+    y = r * sinf(phi);
+}
+
+// Index-matched vial, 3-D ray (Mitsuba's open cylinder with a null BSDF, volume.py:191-216):
+// the first tube hit is the entry only when it is front-facing (else the ray came in through an
+// open end and never enters the medium through the interface: no deposit); o2 is the hit offset
+// inward by spawn_ray's (1 + max|p|) eps (or_segment_index_matched's rule); the segment ends at
+// the next tube hit from o2, and a ray that leaves through an open end has no valid si there
+// (volume.py:268): no deposit either.
+__device__ __forceinline__ bool cn_segment(const TvamConsts& k, ConeRay& r) {
+    const float t0 = sc_tube_hit(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], k.vial_r, k.vial_half_h);
+    if (!(t0 < TVAM_INF)) return false;
+    const float px = fmaf(r.d[0], t0, r.o[0]), py = fmaf(r.d[1], t0, r.o[1]), pz = fmaf(r.d[2], t0, r.o[2]);
+    const float rp = sqrtf(px * px + py * py);
+    const float nx = px / rp, ny = py / rp;
+    const float ndd = nx * r.d[0] + ny * r.d[1] + 0.0f * r.d[2];
+    if (!(ndd < 0.0f)) return false;
+    const float m = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
+    const float mag = -((1.0f + m) * TVAM_RAY_EPS);
+    r.o2[0] = fmaf(mag, nx, px);
+    r.o2[1] = fmaf(mag, ny, py);
+    r.o2[2] = pz;
+    const float t1 = sc_tube_hit(r.o2[0], r.o2[1], r.o2[2], r.d[0], r.d[1], r.d[2], k.vial_r, k.vial_half_h);
+    if (!(t1 < TVAM_INF)) return false;
+    r.maxt = t1;
+    return true;
+}
+
+// The ray of dense shard entry `local`, sample `smp`, and its medium segment.  Returns whether it
+// deposits.  The collimated projector takes tvam_ray_world / tvam_segment_im (the ray records'
+// own expressions), so that the export of such a plan is the oracle's ray bit for bit.
+__device__ __forceinline__ bool cn_ray(const TvamConsts& k, const TvamTiles& tp, const int32_t* idxmap, int64_t local,
+                                       int smp, ConeRay& r) {
+    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
+    const int al = (int)(local / per_angle);
+    const int64_t pix = local - (int64_t)al * per_angle;
+    const int rowc = (int)(pix / k.crop_x), colc = (int)(pix - (int64_t)rowc * k.crop_x);
+    TvamPcg rng;
+    rng.seed(tp.seed, tvam_stream(k, idxmap, local, tp.spp, smp));
+    float jx = 0.5f, jy = 0.5f;
+    if (!k.regular) {
+        jx = rng.next_float();
+        jy = rng.next_float();
+    }
+    float c, sn;
+    if (k.sample_time) {  // common.py:101-104: time = (angle + u) / n_patterns
+        float time = (float)(k.a0 + al);
+        time = time + rng.next_float();
+        time = time / (float)k.n_patterns;
+        float alpha = TVAM_TWO_PI * time;
+        if (k.clockwise) alpha = -alpha;
+        c = cosf(alpha);
+        sn = sinf(alpha);
+    } else {
+        const float2 csv = tp.cs[al];
+        c = csv.x;
+        sn = csv.y;
+    }
+    const float u1 = rng.next_float(), u2 = rng.next_float();  // aperture sample (projector.py:160)
+    float xc, yc;
+    tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
+    if (k.proj_type == TVAM_PROJECTOR_COLLIMATED) {
+        tvam_ray_world(k, c, sn, xc, yc, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1]);
+        r.d[2] = 0.0f;
+        r.o2[2] = r.o[2];
+        return tvam_segment_im(k, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.o2[0], r.o2[1], r.maxt);
+    }
+    float ax, ay;
+    cn_disk(u1, u2, ax, ay);
+    ax = k.ap_r * ax;
+    ay = k.ap_r * ay;
+    // camera space: origin (X, Y, 0) on the aperture plane, direction towards the pixel's point of
+    // the focus plane
+    float X, Y, vx, vy, vz;
+    if (k.proj_type == TVAM_PROJECTOR_TELECENTRIC) {  // projector.py:220-234
+        X = xc + ax;
+        Y = yc + ay;
+        vx = -ax;
+        vy = -ay;
+        vz = 0.005f + k.focus;  // the pixel's point sits on the near plane z_c = 0.005
+    } else {  // projector.py:273-286: focus_p = near_p (focus_distance / near_p.z) = (xc, yc, focus)
+        X = ax;
+        Y = ay;
+        vx = xc - ax;
+        vy = yc - ay;
+        vz = k.focus;
+    }
+    const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
+    vx = vx * inv;
+    vy = vy * inv;
+    vz = vz * inv;
+    // to_world (motion.py:26-36; tvam_ray_world with a general camera point and direction):
+    // (X, Y, Z) -> (c (D - Z) + s X, s (D - Z) - c X, Y), Z = 0
+    const float D = k.dist;
+    r.o[0] = c * D + sn * X;
+    r.o[1] = sn * D - c * X;
+    r.o[2] = Y;
+    r.d[0] = sn * vx - c * vz;
+    r.d[1] = -sn * vz - c * vx;
+    r.d[2] = vy;
+    return cn_segment(k, r);
+}
+
+// The segment's DDA (sensor.py:327-438), stepped like the oracle's or_dda op for op in fp32: the
+// box clip, start / end voxel, dtmax / tstep per axis, then per visit dt = min(dtmax, remaining),
+// dtmax -= dt (an axis at its crossing restarts from tstep), so a ray visits exactly the oracle's
+// voxels (sc_dda's closed-form crossing times fmaf(n, ts, dtm0) can split a near-tie the other
+// way).  The visit weight e^{-st t} (1 - e^{-st dt}) without cancellation (tvam_omexp).  FWD adds
+// em * weight into dose, ADJ returns sum weight * grad * inv_vol, COUNT counts visits.
+template <int MODE>
+__device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], const float d[3], float maxt, float em,
+                                        float* __restrict__ dose, const float* __restrict__ gin, uint64_t& nvis) {
+    float lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float tb0 = (k.bmin[a] - o[a]) / d[a];
+        const float tb1 = (k.bmax[a] - o[a]) / d[a];
+        lo[a] = fminf(tb0, tb1);
+        hi[a] = fmaxf(tb0, tb1);
+    }
+    const float t_start = fmaxf(fmaxf(fmaxf(fmaxf(lo[0], lo[1]), lo[2]), 0.0f), 0.0f);
+    const float t_end = fminf(fminf(fminf(hi[0], hi[1]), hi[2]), maxt);
+    if (!(isfinite(t_start) && isfinite(t_end) && t_start < t_end)) return 0.0f;
+    // axes in scalars (dynamically indexed arrays would be promoted to scratch)
+    int cur[3], endv[3], step[3];
+    float dtm[3], ts[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float gs = fmaf(d[a], t_start, o[a]), ge = fmaf(d[a], t_end, o[a]);
+        step[a] = d[a] > 0.0f ? 1 : -1;
+        int sv = (int)((gs - k.bmin[a]) / k.h[a]);
+        int ev = (int)((ge - k.bmin[a]) / k.h[a]);
+        sv = sv < 0 ? 0 : (sv > k.res[a] - 1 ? k.res[a] - 1 : sv);
+        ev = ev < 0 ? 0 : (ev > k.res[a] - 1 ? k.res[a] - 1 : ev);
+        cur[a] = sv;
+        endv[a] = ev;
+        float next = k.bmin[a] + (float)(sv + step[a]) * k.h[a];
+        if (d[a] < 0.0f) next = next + k.h[a];
+        const bool valid = fabsf(d[a]) > 1e-8f;
+        float dt0 = valid ? (next - gs) / d[a] : TVAM_INF;
+        if (dt0 < 0.0f) dt0 = TVAM_INF;  // sensor.py:358: the axis never steps
+        dtm[a] = dt0;
+        ts[a] = valid ? (k.h[a] / d[a]) * (float)step[a] : TVAM_INF;
+    }
+    const int64_t sy = k.res[0], sz = (int64_t)k.res[0] * k.res[1];
+    float t = t_start, remaining = t_end - t_start, acc = 0.0f;
+    // a ray steps at most res - 1 times per axis (the guard only bounds the loop)
+    const int nmax = k.res[0] + k.res[1] + k.res[2] + 1;
+    for (int it = 0; it < nmax; ++it) {
+        const float dt = fminf(fminf(fminf(dtm[0], dtm[1]), dtm[2]), remaining);
+        remaining = remaining - dt;
+        const int64_t idx = cur[0] + cur[1] * sy + cur[2] * sz;
+        if (MODE != TVAM_MODE_COUNT) {
+            const float c = sc_exp2(k.nsig2 * t) * tvam_omexp(k.sig_t * fmaxf(dt, 0.0f));
+            if (MODE == TVAM_MODE_FWD) atomicAdd(&dose[idx], em * c);
+            else acc = fmaf(c, gin[idx] * k.inv_vol, acc);
+        }
+        ++nvis;
+        const bool alive = (cur[0] != endv[0] || cur[1] != endv[1] || cur[2] != endv[2]) && remaining > 1e-6f;
+        if (!alive) break;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const bool m = dtm[a] == dt;
+            dtm[a] = m ? ts[a] : dtm[a] - dt;
+            cur[a] += m ? step[a] : 0;
+        }
+        if (cur[0] < 0 || cur[1] < 0 || cur[2] < 0 || cur[0] >= k.res[0] || cur[1] >= k.res[1] || cur[2] >= k.res[2])
+            break;
+        t = t + dt;
+    }
+    return acc;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
+                                                        const int32_t* __restrict__ idxmap,
+                                                        const float* __restrict__ gin, float* __restrict__ out,
+                                                        unsigned long long* __restrict__ counter) {
+    const int spp = (int)tp.spp;
+    const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * spp;
+    uint64_t nvis = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t local = i / spp;
+        const int smp = (int)(i - local * spp);
+        float em = 1.0f;
+        int64_t act = local;
+        if (MODE == TVAM_MODE_FWD) {
+            const float p = pat[local];
+            if (p == 0.0f && k.skip_zero) continue;
+            em = p * k.wscale * k.inv_vol;
+        } else if (idxmap) {
+            act = idxmap[local];
+            if (act < 0) continue;
+        }
+        ConeRay r;
+        if (!cn_ray(k, tp, idxmap, local, smp, r)) continue;
+        const float acc = cn_dda<MODE>(k, r.o2, r.d, r.maxt, em, out, gin, nvis);
+        if (MODE == TVAM_MODE_ADJ) {
+            if (spp == 1) out[act] = acc * k.wscale;  // the entry's only ray: no atomic
+            else if (acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
+        }
+    }
+    if (MODE == TVAM_MODE_COUNT) {
+        for (int off = 32; off > 0; off >>= 1) nvis += __shfl_down(nvis, off, 64);
+        if ((threadIdx.x & 63) == 0 && nvis) atomicAdd(counter, (unsigned long long)nvis);
+    }
+}
+
+// One brick-bin record per ray of paths [sb.p0, sb.p1) (sb.slots = 1; the layout of
+// tvam_scatter_kernel<EMIT>'s records: weight em, attenuation 1 for the cached forward's rescale,
+// 0 in slots without a segment), its brick count and the chunk's largest |weight|.
+__global__ __launch_bounds__(256) void tvam_cone_emit_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
+                                                             const int32_t* __restrict__ idxmap, TvamSegBuf sb) {
+    const int spp = (int)tp.spp;
+    float wmax = 0.0f;
+    for (int64_t i = sb.p0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < sb.p1;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t slot = i - sb.p0;
+        reinterpret_cast<float*>(&sb.r[TVAM_REC_F4 * slot + 2])[2] = 0.0f;
+        const int64_t local = i / spp;
+        const int smp = (int)(i - local * spp);
+        const float p = pat[local];
+        if (p == 0.0f && k.skip_zero) continue;
+        const float em = p * k.wscale * k.inv_vol;
+        ConeRay r;
+        if (!cn_ray(k, tp, idxmap, local, smp, r)) continue;
+        SegDda q;
+        if (!sc_dda_init(k, r.o2, r.d, r.maxt, q)) continue;
+        sb.r[TVAM_REC_F4 * slot] = make_float4(q.t_start, q.tau_end, q.dtm0[0], q.dtm0[1]);
+        sb.r[TVAM_REC_F4 * slot + 1] = make_float4(q.dtm0[2], q.ts[0] * (float)q.step[0], q.ts[1] * (float)q.step[1],
+                                                   q.ts[2] * (float)q.step[2]);
+        sb.r[TVAM_REC_F4 * slot + 2] = make_float4(__int_as_float(q.sv[0] | (q.sv[1] << 11) | (q.sv[2] << 22)), em, 1.0f, 0.0f);
+        sb.m[slot] = (uint32_t)sc_brick_count(k, q);
+        wmax = fmaxf(wmax, fabsf(em));
+    }
+    sc_block_max(wmax, sb.wmax);
+}
+
+// tvam_plan_rays: row act * spp + smp = o[3], d[3], hit, o2[3], maxt, d2[3], weight, 0
+__global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, TvamTiles tp,
+                                                               const int32_t* __restrict__ idxmap,
+                                                               float* __restrict__ rays) {
+    const int spp = (int)tp.spp;
+    const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * spp;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t local = i / spp;
+        const int smp = (int)(i - local * spp);
+        int64_t act = local;
+        if (idxmap) {
+            act = idxmap[local];
+            if (act < 0) continue;
+        }
+        ConeRay r;
+        r.o2[0] = r.o2[1] = r.o2[2] = 0.0f;
+        r.maxt = 0.0f;
+        const bool hit = cn_ray(k, tp, idxmap, local, smp, r);
+        float4* row = reinterpret_cast<float4*>(rays + 16 * (act * spp + smp));
+        row[0] = make_float4(r.o[0], r.o[1], r.o[2], r.d[0]);
+        row[1] = make_float4(r.d[1], r.d[2], hit ? 1.0f : 0.0f, hit ? r.o2[0] : 0.0f);
+        row[2] = make_float4(hit ? r.o2[1] : 0.0f, hit ? r.o2[2] : 0.0f, hit ? r.maxt : 0.0f, r.d[0]);
+        row[3] = make_float4(r.d[1], r.d[2], k.wscale, 0.0f);
+    }
+}
+
+unsigned cn_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 262144); }
+
+}  // namespace
+
+hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                                 const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
+                                 hipStream_t stream) {
+    const dim3 g(cn_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp)), b(256);
+    switch (mode) {
+        case TVAM_MODE_FWD:
+            tvam_kt_begin(stream, TVAM_KT_CONE);
+            hipLaunchKernelGGL(tvam_cone_kernel<TVAM_MODE_FWD>, g, b, 0, stream, k, t, pat, idxmap, gin, out, counter);
+            tvam_kt_end(stream, TVAM_KT_CONE);
+            break;
+        case TVAM_MODE_ADJ:
+            hipLaunchKernelGGL(tvam_cone_kernel<TVAM_MODE_ADJ>, g, b, 0, stream, k, t, pat, idxmap, gin, out, counter);
+            break;
+        default:
+            hipLaunchKernelGGL(tvam_cone_kernel<TVAM_MODE_COUNT>, g, b, 0, stream, k, t, pat, idxmap, gin, out, counter);
+    }
+    return hipGetLastError();
+}
+
+void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
+                             const TvamSegBuf& sb, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(tvam_cone_emit_kernel, dim3(grid), dim3(256), 0, stream, k, t, pat, idxmap, sb);
+}
+
+hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
+                                   hipStream_t stream) {
+    const dim3 g(cn_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp)), b(256);
+    hipLaunchKernelGGL(tvam_cone_export_kernel, g, b, 0, stream, k, t, idxmap, rays);
+    return hipGetLastError();
+}

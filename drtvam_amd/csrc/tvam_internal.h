@@ -19,7 +19,7 @@ int tvam_knob(const char* name, int def);
 // Launch timer of the dominant forward kernel (tvam_plan_kernel_time): while enabled, each launch
 // of the measured plan's dominant kind -- the voxel-driven planar forward, the per-ray tile
 // forward or the forward brick march -- is bracketed by two HIP events on its stream.
-enum TvamKtKind { TVAM_KT_PLANAR = 0, TVAM_KT_TILE = 1, TVAM_KT_BRICK = 2 };
+enum TvamKtKind { TVAM_KT_PLANAR = 0, TVAM_KT_TILE = 1, TVAM_KT_BRICK = 2, TVAM_KT_CONE = 3 };
 void tvam_kt_begin(hipStream_t stream, int kind);
 void tvam_kt_end(hipStream_t stream, int kind);
 // the next timer event pair for a launch that records them itself (hipExtLaunchKernelGGL); false: untimed
@@ -253,9 +253,14 @@ hipError_t tvam_launch_scatter_paths(int mode, const TvamConsts& k, const TvamTi
 // Forward of the scattered segments through brick bins (chunks of paths; host
 // syncs once per chunk to size the bins).  Returns hipErrorNotSupported when
 // the grid is too large for the packed records (callers then use the atomics).
+// writer: the record writer of another kind of segment (one record per path: slots = 1, forward
+// only; tvam_cone.hip) in place of tvam_scatter_kernel<EMIT>; it fills sb.r / sb.m / sb.wmax of the
+// paths [sb.p0, sb.p1) on `stream` with `grid` workgroups of 256 threads.
+typedef void (*TvamRecWriter)(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
+                              const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
-                               hipStream_t stream);
+                               hipStream_t stream, TvamRecWriter writer = nullptr);
 void tvam_bin_scratch_free(TvamBinScratch& s);
 
 // Surface-aware films (film_channels 2): every path's medium segment cut at the
@@ -270,6 +275,20 @@ hipError_t tvam_launch_surface_paths(int mode, const TvamConsts& k, const TvamTi
 hipError_t tvam_launch_general_paths(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                      const int32_t* idxmap, const float* gin, float* out,
                                      unsigned long long* counter, hipStream_t stream);
+// The forward such a plan runs with neither TVAM_FLAG_SCATTER_ATOMIC nor TVAM_FLAG_BIN_FIRST:
+// 1 = brick bins, 0 = per-ray atomics.  Measured at 400^3 / 400 angles: the
+// binned forward takes 71 ms (41 ms from the bin cache), the per-ray atomics 1448 ms.
+#define TVAM_CONE_BINNED_DEFAULT 1
+// Telecentric / lens projectors (tvam_cone.hip): every ray's first medium segment is a 3-D ray.
+// Per-ray kernels (forward: global atomics, `out` zeroed by the caller; adjoint: gathers, `out`
+// zeroed by the caller; count), the brick-bin record writer and the ray export.
+hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                                 const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
+                                 hipStream_t stream);
+void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
+                             const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
+hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
+                                   hipStream_t stream);
 hipError_t tvam_launch_scale_volumes(int64_t n, const float* vols, float* dose, hipStream_t stream);
 // compute_volume (sensor.py:47-110): volumes [res z][y][x][2]
 hipError_t tvam_launch_volumes(const TvamConsts& k, uint32_t sample_count, float* volumes, hipStream_t stream);

@@ -47,6 +47,7 @@ struct tvam_plan {
     bool cyl;    // refracting (cylindrical / square) vial: per-ray directions and weights
     bool surface = false;    // surface-aware film (2 channels): per-path kernels cut at the target mesh
     bool general = false;    // sample_time or a ratio / delta sensor: the general per-path kernel
+    bool cone = false;       // telecentric / lens projector: 3-D first segments (tvam_cone.hip); implies general
     float* d_tgt = nullptr;  // target mesh triangles (surface-aware films)
     const float* vols = nullptr;  // caller's compute_volume() output (tvam_plan_set_volumes)
     float* d_occ = nullptr;  // occluder triangles
@@ -221,8 +222,28 @@ extern "C" void tvam_plan_destroy(tvam_plan* p) {
 
 static int validate(const tvam_desc& d) {
     if (d.abi_version != TVAM_ABI_VERSION) return fail(TVAM_ERR_INVALID, "tvam_desc.abi_version mismatch");
-    if (d.projector_type != TVAM_PROJECTOR_COLLIMATED)
-        return fail(TVAM_ERR_UNSUPPORTED, "only the 'collimated' projector is implemented on the GPU path");
+    if (d.projector_type != TVAM_PROJECTOR_COLLIMATED && d.projector_type != TVAM_PROJECTOR_TELECENTRIC &&
+        d.projector_type != TVAM_PROJECTOR_LENS)
+        return fail(TVAM_ERR_UNSUPPORTED, "only the 'collimated', 'telecentric' and 'lens' projectors are implemented on the GPU path");
+    if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
+        // 3-D projector rays (tvam_cone.hip): index-matched vial, absorbing medium, 'dda' sensor,
+        // one-channel film, the whole film
+        const char* pn = d.projector_type == TVAM_PROJECTOR_LENS ? "'lens'" : "'telecentric'";
+        auto no = [&](const char* what) {
+            return fail(TVAM_ERR_UNSUPPORTED, std::string("the ") + pn + " projector with " + what +
+                                                  " is not implemented on the GPU path");
+        };
+        if (!(d.focus_distance > 0.0f)) return fail(TVAM_ERR_INVALID, "focus_distance must be positive");
+        if (!(d.aperture_radius >= 0.0f)) return fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
+        if (d.vial_type == TVAM_VIAL_CYLINDRICAL) return no("a 'cylindrical' vial (3-D refraction)");
+        if (d.vial_type == TVAM_VIAL_SQUARE) return no("a 'square' vial (3-D refraction)");
+        if (d.n_occluder_tris > 0) return no("occluders");
+        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
+        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
+        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
+        if (d.film_channels == 2) return no("a surface-aware film");
+        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
+    }
     if (d.sensor_type != TVAM_SENSOR_DDA && d.sensor_type != TVAM_SENSOR_RATIO && d.sensor_type != TVAM_SENSOR_DELTA)
         return fail(TVAM_ERR_INVALID, "unknown sensor type");
     if (d.sensor_type == TVAM_SENSOR_DELTA && d.albedo == 0.0f)  // volume.py:160-161
@@ -332,6 +353,10 @@ static TvamConsts make_consts(const tvam_desc& d, int a0, int a1) {
     k.sensor_type = d.sensor_type;
     k.majorant = d.majorant;
     k.wscale = 0.0f;  // per call
+    k.proj_type = d.projector_type;
+    k.ap_r = d.aperture_radius;
+    k.focus = d.focus_distance;
+    k.dist = d.distance;
     {
         double hxy = std::max((double)k.h[0], (double)k.h[1]);
         k.vox_chord = (float)std::min(1.0, (double)d.sigma_t * std::sqrt(2.0) * hxy);
@@ -1127,7 +1152,8 @@ extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** o
     // surfaces + medium segment (volume.py:179, :271-272)
     p->empty = d.max_depth < (p->cyl ? 3 : 2);
     p->surface = d.film_channels == 2;
-    p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA);
+    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED;
+    p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
     if (p->surface) {  // target mesh to the device (TvamConsts::tgt)
         std::vector<float> tri(d.target_tris, d.target_tris + 9 * (size_t)d.n_target_tris);
         if ((rc = upload(&p->d_tgt, tri))) {
@@ -1612,6 +1638,22 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
         TvamTiles t = p->tiles;
         t.spp = spp;
         t.seed = seed;
+        if (p->cone) {
+            // the brick-binned forward or the per-ray atomics: by flag, else the plan's default
+            const int fl = p->desc.flags;
+            const bool binned = (fl & TVAM_FLAG_BIN_FIRST) || (!(fl & TVAM_FLAG_SCATTER_ATOMIC) && TVAM_CONE_BINNED_DEFAULT);
+            e = hipErrorNotSupported;
+            p->bins.acc_float = env_int("TVAM_BIN_FLOAT", 0);
+            if (binned)
+                e = tvam_scatter_binned(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, p->bins, stream,
+                                        tvam_cone_write_records);
+            else
+                for (auto& v : p->bins.st) v = 0;  // nothing binned
+            if (e == hipErrorNotSupported)  // (grids beyond the packed records' range)
+                e = tvam_launch_cone_rays(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, nullptr, stream);
+            if (e == hipErrorIllegalState) return bin_mismatch_fail(p);
+            return e == hipSuccess ? 0 : hip_fail(e, "projector-ray forward launch");
+        }
         e = tvam_launch_general_paths(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, nullptr, stream);
         return e == hipSuccess ? 0 : hip_fail(e, "path forward launch");
     }
@@ -1767,7 +1809,8 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
         TvamTiles t = p->tiles;
         t.spp = spp;
         t.seed = seed;
-        e = tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
+        e = p->cone ? tvam_launch_cone_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+                    : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
         return e == hipSuccess ? 0 : hip_fail(e, "path adjoint launch");
     }
     if (p->surface) {
@@ -1811,6 +1854,35 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     return 0;
 }
 
+// The rays of a call (tvam_cone.hip's ray generation serves every projector kind).
+extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
+                              uint32_t seed, float* rays, void* stream_) {
+    if (!p || (!rays && n_active)) return fail(TVAM_ERR_INVALID, "null argument");
+    const tvam_desc& d = p->desc;
+    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED || d.albedo != 0.0f || d.n_occluder_tris > 0)
+        return fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched plans without scattering or occluders only");
+    hipStream_t stream = (hipStream_t)stream_;
+    TvamConsts k;
+    int rc = call_setup(p, n_active, active_pixels, spp, k);
+    if (rc) return rc;
+    if (n_active == 0) return 0;
+    hipError_t e;
+    const int32_t* idxmap = nullptr;
+    if (active_pixels) {
+        if ((rc = ensure_dense(p))) return rc;
+        if ((e = hipMemsetAsync(p->d_idxmap, 0xff, p->dense_n * sizeof(int32_t), stream)) != hipSuccess)
+            return hip_fail(e, "hipMemsetAsync");
+        if ((e = tvam_launch_scatter(k, nullptr, active_pixels, n_active, p->d_dense, p->d_idxmap, stream)) != hipSuccess)
+            return hip_fail(e, "scatter launch");
+        idxmap = p->d_idxmap;
+    }
+    TvamTiles t = p->tiles;
+    t.spp = spp;
+    t.seed = seed;
+    e = tvam_launch_cone_export(k, t, idxmap, rays, stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "ray export launch");
+}
+
 extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint64_t* visits) {
     if (!p || !visits) return fail(TVAM_ERR_INVALID, "null argument");
     TvamConsts k;
@@ -1826,7 +1898,8 @@ extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint
     t.spp = spp;
     t.seed = seed;
     if (p->general) {
-        e = tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->d_counter, nullptr);
+        e = p->cone ? tvam_launch_cone_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->d_counter, nullptr)
+                    : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->d_counter, nullptr);
     } else if (p->surface) {
         e = tvam_launch_surface_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, nullptr, p->d_counter,
                                       nullptr);
@@ -1854,6 +1927,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
     if (!p || !radon || n_target_tris < 0 || (n_target_tris > 0 && !target_tris))
         return fail(TVAM_ERR_INVALID, "null argument");
     const tvam_desc& d = p->desc;
+    if (p->cone)  // the Radon path is a planar ray (tvam_radon_ray)
+        return fail(TVAM_ERR_UNSUPPORTED, "the 'telecentric' / 'lens' projectors with filter_radon are not implemented on the GPU path");
     const uint64_t n = (uint64_t)(p->k.a1 - p->k.a0) * d.crop_y * d.crop_x;
     TvamConsts k;
     int rc = call_setup(p, n, nullptr, spp, k);
@@ -1940,7 +2015,10 @@ extern "C" int tvam_plan_fwd_scale(tvam_plan* p, float* scale) {
 }
 
 // bit 0: planar adjoint (+ ray-driven planar forward unless bit 1), bit 1: voxel-driven planar forward
-extern "C" int tvam_plan_path(const tvam_plan* p) { return p ? (p->planar ? 1 : 0) | (p->planar_fwd ? 2 : 0) : 0; }
+// bit 2: 3-D projector rays (telecentric / lens)
+extern "C" int tvam_plan_path(const tvam_plan* p) {
+    return p ? (p->planar ? 1 : 0) | (p->planar_fwd ? 2 : 0) | (p->cone ? 4 : 0) : 0;
+}
 
 extern "C" int tvam_plan_stats(tvam_plan* p, uint64_t* fallback_tiles) {
     if (!p || !fallback_tiles) return fail(TVAM_ERR_INVALID, "null argument");
@@ -2037,7 +2115,11 @@ extern "C" int tvam_plan_kernel_time(tvam_plan* p, int32_t enable, double* total
         }
         // the plan's dominant forward kernel: the brick march of a scattering medium, else the
         // voxel-driven planar forward where it serves, else the per-ray tile forward
-        g_kt.kind = p->desc.albedo != 0.0f ? TVAM_KT_BRICK : (p->planar_fwd ? TVAM_KT_PLANAR : TVAM_KT_TILE);
+        // (telecentric / lens: the brick march of the binned forward, else the per-ray atomic forward)
+        const bool cone_binned = p->cone && ((p->desc.flags & TVAM_FLAG_BIN_FIRST) ||
+                                             (!(p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC) && TVAM_CONE_BINNED_DEFAULT));
+        g_kt.kind = p->cone ? (cone_binned ? TVAM_KT_BRICK : TVAM_KT_CONE)
+                            : (p->desc.albedo != 0.0f ? TVAM_KT_BRICK : (p->planar_fwd ? TVAM_KT_PLANAR : TVAM_KT_TILE));
         g_kt.on = true;
     }
     return 0;
@@ -2224,6 +2306,8 @@ extern "C" int tvam_row_slices(const tvam_desc* desc, int32_t* slice_of_row) {
     int rc = validate(*desc);
     if (rc) return rc;
     const tvam_desc& d = *desc;
+    if (d.projector_type != TVAM_PROJECTOR_COLLIMATED)  // 3-D rays cross slices: no row <-> slice map
+        return fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: the 'telecentric' / 'lens' projectors' rays leave their slice (no film slabs)");
     const TvamConsts k = make_consts(d, 0, d.n_patterns);
     for (int r = 0; r < d.crop_y; ++r) {
         float xc, yc;

@@ -25,24 +25,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "tvam_bricks.h"
+#include "tvam_seg3d.h"
 
 namespace {
-
-__device__ __forceinline__ float sc_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// Nearest hit t >= 0 of the open tube (radius r, |z| <= half) for a 3-D ray
-// (Mitsuba cylinder restated; oracle or_tube_hit).
-__device__ __forceinline__ float sc_tube_hit(float ox, float oy, float oz, float dx, float dy, float dz, float r,
-                                             float half) {
-    float t0, t1;
-    if (!tvam_cyl_roots(ox, oy, dx, dy, r, t0, t1)) return TVAM_INF;
-    if (!(t1 >= 0.0f)) return TVAM_INF;
-    const float zn = fmaf(dz, t0, oz), zf = fmaf(dz, t1, oz);
-    if (t0 >= 0.0f && zn >= -half && zn <= half) return t0;
-    if (zf >= -half && zf <= half) return t1;
-    return TVAM_INF;
-}
 
 // Next container surface from inside the medium (the inner / index-matched tube
 // comes first; the outer tube is only reached through it).
@@ -126,66 +111,7 @@ __device__ __forceinline__ void sc_phase(const TvamConsts& k, float dx, float dy
 // ---------------------------------------------------------------------------
 // SegDda, sc_dda_init, sc_walk_bricks, sc_brick_count: tvam_bricks.h
 
-// The visits of a segment inside the voxel box [lo, hi) (a brick), resumed in
-// closed form at the box entry: per axis the step count n at the entry time,
-// the next crossing at t = dtm0 + n ts (fmaf from the count, so a visit splits
-// at a brick face exactly where the neighbouring brick resumes), one axis per
-// visit (ties: x before y before z).  Axes are kept in scalars (dynamically
-// indexed arrays would be promoted to LDS).  F(local x, y, z, weight
-// e^{-st t0} - e^{-st t1}).
-template <typename F>
-__device__ __forceinline__ void sc_box_march(const TvamConsts& k, const SegDda& q, const int lo[3], const int hi[3],
-                                             F&& f) {
-    float tin[3], tout[3];
-    int nin[3], nout[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        tvam_axis_window(q.sv[a], q.step[a], q.dtm0[a], q.ts[a], lo[a], hi[a], tin[a], tout[a], nin[a], nout[a]);
-    const float tau_e = fmaxf(fmaxf(fmaxf(tin[0], tin[1]), tin[2]), 0.0f);
-    const float tau_x = fminf(fminf(fminf(tout[0], tout[1]), tout[2]), q.tau_end);
-    if (!(tau_e < tau_x)) return;
-    int n0 = tvam_axis_steps(tau_e, q.dtm0[0], q.ts[0], nin[0], nout[0]);
-    int n1 = tvam_axis_steps(tau_e, q.dtm0[1], q.ts[1], nin[1], nout[1]);
-    int n2 = tvam_axis_steps(tau_e, q.dtm0[2], q.ts[2], nin[2], nout[2]);
-    int x = q.sv[0] + q.step[0] * n0 - lo[0];
-    int y = q.sv[1] + q.step[1] * n1 - lo[1];
-    int z = q.sv[2] + q.step[2] * n2 - lo[2];
-    const float ts0 = q.ts[0], ts1 = q.ts[1], ts2 = q.ts[2];
-    const float d0 = q.dtm0[0], d1 = q.dtm0[1], d2 = q.dtm0[2];
-    float T0 = d0 < TVAM_INF ? fmaf((float)n0, ts0, d0) : TVAM_INF;
-    float T1 = d1 < TVAM_INF ? fmaf((float)n1, ts1, d1) : TVAM_INF;
-    float T2 = d2 < TVAM_INF ? fmaf((float)n2, ts2, d2) : TVAM_INF;
-    const int s0 = q.step[0], s1 = q.step[1], s2 = q.step[2];
-    const float stop = tau_x - 1e-6f;
-    const float base = k.nsig2 * q.t_start;
-    float ea = sc_exp2(fmaf(k.nsig2, tau_e, base)), tp = tau_e;
-    for (int guard = 0; guard < 3 * 4096; ++guard) {
-        const bool m0 = T0 <= T1 && T0 <= T2;
-        const bool m1 = !m0 && T1 <= T2;
-        const float tmin = m0 ? T0 : (m1 ? T1 : T2);
-        const float tn = tmin < tau_x ? tmin : tau_x;
-        // e^{-st t} (1 - e^{-st dt}) without cancellation (tvam_omexp); ea tracks e^{-st t}
-        const float c = ea * tvam_omexp(k.sig_t * fmaxf(tn - tp, 0.0f));
-        const float eb = ea - c;
-        tp = tn;
-        f(x, y, z, c);
-        if (!(tn < stop)) break;
-        if (m0) {
-            x += s0;
-            ++n0;
-            T0 = fmaf((float)n0, ts0, d0);
-        } else if (m1) {
-            y += s1;
-            ++n1;
-            T1 = fmaf((float)n1, ts1, d1);
-        } else {
-            z += s2;
-            ++n2;
-            T2 = fmaf((float)n2, ts2, d2);
-        }
-        ea = eb;
-    }
-}
+// sc_tube_hit, sc_box_march, sc_seg_march, sc_dda: tvam_seg3d.h
 
 // sc_box_march for the brick kernels: the same visits (the same crossing times fmaf(n, ts, dtm0)
 // and axis choices), stepped without divergent branches (every axis' candidate next crossing is
@@ -252,52 +178,8 @@ __device__ __forceinline__ void sc_brick_march(const TvamConsts& k, const SegDda
     }
 }
 
-// The whole segment, brick by brick (the binned forward's visits exactly).
-template <typename F>
-__device__ __forceinline__ void sc_seg_march(const TvamConsts& k, const SegDda& q, F&& f) {
-    const int B[3] = {TVAM_BX, TVAM_BY, TVAM_BZ};
-    const int nb[3] = {sc_nbr(k, 0), sc_nbr(k, 1), sc_nbr(k, 2)};
-    sc_walk_bricks(k, q, [&](int bid, float, float) {
-        const int bx = bid % nb[0], by = (bid / nb[0]) % nb[1], bz = bid / (nb[0] * nb[1]);
-        const int lo[3] = {bx * B[0], by * B[1], bz * B[2]};
-        const int hi[3] = {min(lo[0] + B[0], k.res[0]), min(lo[1] + B[1], k.res[1]), min(lo[2] + B[2], k.res[2])};
-        sc_box_march(k, q, lo, hi, [&](int x, int y, int z, float c) { f(lo[0] + x, lo[1] + y, lo[2] + z, c); });
-    });
-}
 
-// One medium segment's 3-D DDA (sensor.py:327-438, op for op like the oracle's
-// or_dda): MODE FWD adds em * (e^{-st t} - e^{-st (t + dt)}) * inv_vol into the
-// dose, ADJ returns sum (...) * grad * inv_vol, COUNT counts visits.
-template <int MODE>
-__device__ float sc_dda(const TvamConsts& k, float ox, float oy, float oz, float dx, float dy, float dz, float maxt,
-                        float em, float* __restrict__ dose, const float* __restrict__ gin, uint64_t& nvis) {
-    const float o[3] = {ox, oy, oz}, d[3] = {dx, dy, dz};
-    SegDda q;
-    if (!sc_dda_init(k, o, d, maxt, q)) return 0.0f;
-    float acc = 0.0f;
-    const int64_t sy = k.res[0], sz = (int64_t)k.res[0] * k.res[1];
-    sc_seg_march(k, q, [&](int x, int y, int z, float c) {
-        const int64_t idx = x + y * sy + z * sz;
-        if (MODE == TVAM_MODE_FWD) atomicAdd(&dose[idx], em * c);
-        else if (MODE == TVAM_MODE_ADJ) acc = fmaf(c, gin[idx] * k.inv_vol, acc);
-        ++nvis;
-    });
-    return acc;
-}
-
-// The largest of a 256-thread workgroup's non-negative values into *dst (float bits, which order
-// like the floats): one device atomic per workgroup (one per wave put ~10^6 atomics on a single
-// address per chunk)
-__device__ __forceinline__ void sc_block_max(float v, uint32_t* dst) {
-    __shared__ float s_max[4];
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        v = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-        if (v > 0.0f) atomicMax(dst, __float_as_uint(v));
-    }
-}
+// sc_block_max: tvam_seg3d.h
 
 template <int MODE>
 __global__ __launch_bounds__(256) void tvam_scatter_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
@@ -1721,7 +1603,7 @@ void tvam_bin_scratch_free(TvamBinScratch& s) {
 
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
-                               hipStream_t stream) {
+                               hipStream_t stream, TvamRecWriter writer) {
     for (int i = 0; i < 5; ++i) s.st[i] = 0;  // stats of this call, also when it bins nothing
     // an earlier call's count check, if its copy has landed: a slot whose brick walk disagreed with
     // the writer's closed-form count (never, by construction) may have dropped entries -- fail loudly
@@ -1730,8 +1612,10 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         if (*s.bad_host) return hipErrorIllegalState;
     }
     const int nsurf = k.vial_type == 0 ? 1 : 2;
-    const int slots = k.max_depth - nsurf - 1;  // later medium segments per path
+    // later medium segments per path; a record writer of first segments writes one per path
+    const int slots = writer ? 1 : k.max_depth - nsurf - 1;
     if (slots <= 0) return hipSuccess;
+    if (writer && mode != TVAM_MODE_FWD) return hipErrorNotSupported;
     if (k.res[0] > 2048 || k.res[1] > 2048 || k.res[2] > 1024) return hipErrorNotSupported;
     const bool adj = mode == TVAM_MODE_ADJ;
     const int nbx = (k.res[0] + TVAM_BX - 1) / TVAM_BX, nby = (k.res[1] + TVAM_BY - 1) / TVAM_BY,
@@ -1752,6 +1636,9 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
     const int64_t npaths = (int64_t)t.n_shard * k.crop_y * k.crop_x * spp;
     // chunk of paths: a whole number of pixels (the adjoint reduces a pixel's samples together)
     int64_t max_slots = (int64_t)1 << 27;  // 128M slots (TVAM_BIN_CHUNK_SLOTS: smaller, for tests)
+    // a writer's segments cross the whole grid (up to nbx + nby + nbz bricks each, where a scattered
+    // segment crosses a few): 16M per chunk, and fewer where the chunk's entries could pass 2^31
+    if (writer) max_slots = std::min<int64_t>((int64_t)1 << 24, (((int64_t)1 << 31) - 1) / (nbx + nby + nbz));
     if (const int cs = tvam_knob("TVAM_BIN_CHUNK_SLOTS", 0)) max_slots = std::max<int64_t>(1, cs);
     int64_t chunk = std::max<int64_t>(1, max_slots / slots);
     chunk = std::max<int64_t>(spp, chunk / spp * spp);
@@ -1766,7 +1653,7 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
     // of 5.6, and the brick marches lose the record-line sharing of the class-sorted fill order
     // (forward 18.8 -> 23.7 ms, adjoint 16.2 -> 20.1 ms per chunk): 0.2856 -> 0.2853 it/s.
     static const bool bin_sort = tvam_knob("TVAM_BIN_SORT", 1) != 0;
-    const bool csort = !bin_sort && !s.acc_float && bin_nt == 1024 && nbricks <= 16384 &&
+    const bool csort = !writer && !bin_sort && !s.acc_float && bin_nt == 1024 && nbricks <= 16384 &&
                        nsl <= ((int64_t)1 << TVAM_ENT_SLOT_BITS);
     hipError_t e;
     if (nsl > s.cap_slots) {
@@ -1892,9 +1779,12 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         } else {
             sb.hist = nullptr;
         }
-        hipLaunchKernelGGL(tvam_scatter_kernel<TVAM_MODE_EMIT>, dim3((unsigned)g), dim3(256),
-                           csort ? (size_t)nbricks * sizeof(uint32_t) : 0, stream, k, t, pat, idxmap, nullptr, nullptr,
-                           nullptr, sb);
+        if (writer)
+            writer(k, t, pat, idxmap, sb, (unsigned)g, stream);
+        else
+            hipLaunchKernelGGL(tvam_scatter_kernel<TVAM_MODE_EMIT>, dim3((unsigned)g), dim3(256),
+                               csort ? (size_t)nbricks * sizeof(uint32_t) : 0, stream, k, t, pat, idxmap, nullptr,
+                               nullptr, nullptr, sb);
         sb.hist = nullptr;  // the march kernels read none of it
         if (csort) {
             size_t tbh = 0;

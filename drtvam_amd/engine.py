@@ -190,6 +190,32 @@ class Projection:
                                            seed & 0xFFFFFFFF, max_depth, out.data_ptr(), _stream_ptr(self.device)))
         return out
 
+    def rays(self, n_active: Optional[int] = None, active_pixels: Optional[torch.Tensor] = None, spp: int = 1,
+             seed: int = 0) -> torch.Tensor:
+        """The projector rays of a call (tvam_plan_rays), [n_active * spp, 16] float32 in sampler-stream
+        order (row = active entry * spp + sample): o[0:3], d[3:6], hit [6], o2[7:10], maxt [10],
+        d2[11:14], weight [14] (the whole per-ray weight), 0.  The diagnostic counterpart of the
+        oracle's ray(); index-matched plans with a non-scattering medium."""
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+            n_active = int(active_pixels.numel())
+        elif n_active is None:
+            a0, a1 = self.desc.angle_begin, (self.desc.angle_end if self.desc.angle_end >= 0 else self.desc.n_patterns)
+            n_active = (a1 - a0) * self.desc.crop_y * self.desc.crop_x
+        if self.desc.regular_sampling:
+            spp = 1  # common.py:49-51
+        out = torch.zeros((int(n_active) * int(spp), 16), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_plan_rays(
+                self._plan, None if active_pixels is None else active_pixels.data_ptr(), int(n_active), int(spp),
+                seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    @property
+    def cone(self) -> bool:
+        """True for the 3-D projector rays of a telecentric / lens projector."""
+        return bool(self.lib.tvam_plan_path(self._plan) & 4)
+
     @property
     def planar(self) -> bool:
         """True when the planar fast path (regular sampling) serves this plan's adjoint."""

@@ -489,9 +489,10 @@ class TvamProblem(ShardedLoop):
         self.crop_x, self.crop_y = p.crop[0], p.crop[1]
         full_desc = VolumeIntegrator(base).desc(self.scene, self.sensor)
         self.res_z = int(full_desc.film_res[2])
-        if 'flags' not in config and full_desc.albedo != 0.0:
+        if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0):
             # every path marched, as the reference marches every active pixel (projector.py:66-70,
-            # common.py:81-82): a scattering scene's paths then do not depend on the pattern, and
+            # common.py:81-82): a scattering scene's paths (and a telecentric / lens projector's
+            # binned first segments) then do not depend on the pattern, and
             # the line-search forward is served from the forward bin cache (lbfgs.py:240-249)
             from ._abi import FLAG_NO_ZERO_SKIP
             base['flags'] = int(base['flags']) | FLAG_NO_ZERO_SKIP
@@ -506,7 +507,15 @@ class TvamProblem(ShardedLoop):
                                          config['target'].get('analytic', 'box_hole'))
         self.target_full = target.to(dtype=torch.float32)
         # scattered paths leave their slice; surface-aware films run the per-path kernels
-        planar = self.regular_sampling and full_desc.albedo == 0.0 and not self.surface_aware
+        # a telecentric / lens projector's rays cross slices too (3-D first segments)
+        cone = int(full_desc.projector_type) != 0
+        if cone and shard == 'slab':
+            raise ValueError("z-slab sharding needs planar rays: the 'telecentric' and 'lens' projectors' rays "
+                             "leave their slice (use shard 'angle')")
+        if cone and config.get('filter_radon', False) and filter_pixels:
+            raise NotImplementedError("filter_radon with the 'telecentric' / 'lens' projectors is not implemented "
+                                      "on the GPU path")
+        planar = self.regular_sampling and full_desc.albedo == 0.0 and not self.surface_aware and not cone
         if shard == 'slab' and not (planar and fusable):
             raise ValueError("z-slab sharding needs regular sampling, a non-scattering medium and the fused "
                              "thresholded loss")

@@ -196,23 +196,76 @@ class CollimatedProjector(TVAMProjector):
                 ']')
 
 
+def _pixel_size_2(ps):
+    """'pixel_size' as (a_x, a_y): a float or a Point2f (projector.py:208-211)."""
+    if isinstance(ps, (int, float)):
+        return (float(ps), float(ps))
+    if isinstance(ps, (tuple, list)) and len(ps) == 2:
+        return (float(ps[0]), float(ps[1]))
+    raise ValueError("[self.__class__.__name__] pixel_size must be a float or a Point2f")
+
+
 class TelecentricProjector(TVAMProjector):
-    """Telecentric lens projector (projector.py:199-237); not on the GPU path yet."""
+    """Telecentric lens projector (projector.py:199-237): every pixel's chief ray is parallel to
+    the projector axis; its rays start on an aperture disk of radius ``aperture_radius`` around the
+    pixel and converge on the pixel's point at ``focus_distance``."""
 
     def __init__(self, props):
         super().__init__(props)
-        self.pixel_size = props['pixel_size']
-        self.aperture_radius = props['aperture_radius']
-        self.focus_distance = props['focus_distance']
+        self.pixel_size = _pixel_size_2(props['pixel_size'])
+        self.aperture_radius = float(props['aperture_radius'])
+        self.focus_distance = float(props['focus_distance'])
+        self.emitter_size = (self.res[0] * self.pixel_size[0], self.res[1] * self.pixel_size[1])
+
+    def fill_desc(self, desc):
+        self._fill_common(desc)
+        desc.projector_type = _abi.PROJECTOR_TELECENTRIC
+        desc.pixel_size_x, desc.pixel_size_y = self.pixel_size
+        desc.aperture_radius = self.aperture_radius
+        desc.focus_distance = self.focus_distance
+
+    def to_string(self):
+        return 'TelecentricProjector'
 
 
 class LensProjector(TVAMProjector):
-    """Perspective lens projector (projector.py:241-296); not on the GPU path yet."""
+    """Perspective thin-lens projector (projector.py:241-296): rays start on the lens aperture at
+    the projector position and pass their pixel's point of the plane at ``focus_distance``, where a
+    pixel measures ``pixel_size`` (given directly, or through the horizontal field of view ``fov``
+    in degrees)."""
 
     def __init__(self, props):
         super().__init__(props)
-        self.aperture_radius = props['aperture_radius']
-        self.focus_distance = props['focus_distance']
+        self.aperture_radius = float(props['aperture_radius'])
+        self.focus_distance = float(props['focus_distance'])
+
+        assert not ('fov' in props and 'pixel_size' in props), "Specify either 'fov' or 'pixel_size', not both."
+        assert ('fov' in props or 'pixel_size' in props), "Either 'fov' or 'pixel_size' must be specified."
+        if 'fov' in props:
+            self.fov = float(props['fov'])
+            # pixel_size * N_x = tan(fov / 2) * 2 * focus_distance (projector.py:254-255), in double
+            self.pixel_size = float(np.tan(np.deg2rad(self.fov) / 2) * 2 * self.focus_distance / self.res[0])
+        if 'pixel_size' in props:
+            self.pixel_size = float(props['pixel_size'])
+            self.fov = float(np.rad2deg(2 * np.arctan(self.pixel_size * self.res[0] / 2 / self.focus_distance)))
+        # image rectangle on the plane z = 1 (projector.py:267-271)
+        self.area = (self.pixel_size / self.focus_distance) ** 2 * self.res[0] * self.res[1]
+
+    def fill_desc(self, desc):
+        self._fill_common(desc)
+        desc.projector_type = _abi.PROJECTOR_LENS
+        desc.pixel_size_x = desc.pixel_size_y = self.pixel_size
+        desc.aperture_radius = self.aperture_radius
+        desc.focus_distance = self.focus_distance
+
+    def to_string(self):
+        return ('LensProjector[\n'
+                f'    fov = {self.fov},\n'
+                f'    aperture radius = {self.aperture_radius},\n'
+                f'    focus distance = {self.focus_distance},\n'
+                f'    pattern count = {self.n_patterns},\n'
+                f'    pattern resolution = {self.res},\n'
+                ']')
 
 
 emitters = {

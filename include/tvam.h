@@ -3,12 +3,13 @@
  *
  * This is the drop-in boundary for Dr.TVAM's hot path: the per-angle voxel-grid
  * ray march behind the `volume` integrator + `dda` sensor + `vfilm` film +
- * `collimated` projector plugins.  Every entry point names the reference
+ * `collimated` / `telecentric` / `lens` projector plugins.  Every entry point names the reference
  * interface it replaces (paths relative to the drtvam source tree):
  *
  *   tvam_plan_create   <- scene assembly: optimize.py:15-79 (load_scene),
  *                         TVAMProjector.__init__ projector.py:41-139,
  *                         CollimatedProjector.__init__ projector.py:167-182,
+ *                         TelecentricProjector / LensProjector.__init__ projector.py:199-271,
  *                         CircularMotion motion.py:19-36,
  *                         VolumetricSensor.__init__ sensor.py:5-22,
  *                         VolumetricFilm.__init__ film.py:4-21,
@@ -45,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TVAM_ABI_VERSION 12
+#define TVAM_ABI_VERSION 13
 
 /* error codes */
 #define TVAM_OK               0
@@ -56,6 +57,8 @@ extern "C" {
 
 /* projector kinds (projector.py:300-302) */
 #define TVAM_PROJECTOR_COLLIMATED 0
+#define TVAM_PROJECTOR_TELECENTRIC 1  /* projector.py:199-237: parallel chief rays, finite aperture */
+#define TVAM_PROJECTOR_LENS        2  /* projector.py:241-296: thin lens, chief rays through the lens centre */
 /* vial / container kinds (geometry.py:312-318) */
 #define TVAM_VIAL_INDEX_MATCHED   0
 #define TVAM_VIAL_CYLINDRICAL     1
@@ -154,6 +157,13 @@ typedef struct tvam_desc {
        (projector.py:164-165, :187) in the reference's fp32 rounding; 0 = the call's
        n_active. */
     int64_t active_total;
+    /* 'telecentric' / 'lens' projectors (ABI v13; projector.py:204-205, :245-246): every ray starts
+       on the aperture disk (radius aperture_radius, sampled with square_to_uniform_disk_concentric)
+       and passes its pixel's point of the plane at focus_distance.  'lens': pixel_size_x =
+       pixel_size_y = the pixel size at the focus plane (from 'fov' or 'pixel_size',
+       projector.py:252-262).  Unused by 'collimated'. */
+    float   aperture_radius;
+    float   focus_distance;
 } tvam_desc;
 
 /* tvam_desc.flags */
@@ -161,7 +171,10 @@ typedef struct tvam_desc {
 #define TVAM_FLAG_FWD_STATS    2  /* forward: count tiles that fell back to float LDS atomics */
 #define TVAM_FLAG_NO_PLANAR    4  /* use the per-ray tile kernels even where the planar path applies */
 #define TVAM_FLAG_RAY_FWD      8  /* planar path: ray-driven forward instead of the voxel-driven one */
-#define TVAM_FLAG_SCATTER_ATOMIC 16 /* scattering media: per-path global atomics / gathers instead of brick bins */
+#define TVAM_FLAG_SCATTER_ATOMIC 16 /* scattering media: per-path global atomics / gathers instead of brick bins;
+                                       telecentric / lens projectors: the per-ray atomic forward */
+#define TVAM_FLAG_BIN_FIRST    32  /* telecentric / lens projectors: the brick-binned forward (neither flag: the
+                                       plan's default forward) */
 
 typedef struct tvam_plan tvam_plan;
 
@@ -302,7 +315,8 @@ int tvam_plan_set_volumes(tvam_plan* plan, const float* volumes);
 /* Which kernels serve this plan (bit mask; 0 = per-ray tile kernels):
    bit 0 = planar adjoint (regular sampling: one ray record per (angle,
    column), Z-slice-sharing adjoint); bit 1 = voxel-driven planar forward
-   (straight rays only: not behind a refracting vial). */
+   (straight rays only: not behind a refracting vial); bit 2 = 3-D projector
+   rays (telecentric / lens: tvam_cone.hip; ABI v13). */
 int tvam_plan_path(const tvam_plan* plan);
 
 /*
@@ -391,6 +405,19 @@ int tvam_adjoint_slices(tvam_plan* plan, const float* grad_dose, uint64_t n_acti
                         int32_t row_begin, int32_t row_end, float* grad_active, void* hip_stream);
 /* Slice granularity of tvam_adjoint_slices (0: not available). */
 int tvam_plan_adj_chunk(const tvam_plan* plan);
+
+/*
+ * Diagnostics (ABI v13): the projector rays of a call, as tvam_forward / tvam_adjoint generate them
+ * (get_ray projector.py:184-188, :220-234, :273-286; to_world motion.py:26-36; the medium segment
+ * volume.py:191-216).  rays: device, [n_active * spp][16] f32, row active entry * spp + sample
+ * (sampler-stream order) = o[3], d[3], hit (0 / 1), o2[3], maxt, d2[3], weight, 0: the ray, whether
+ * it deposits, its medium segment (o2, d2, [0, maxt]) and its whole weight (inv_pdf / n_samples *
+ * print_time * sigma_a / sigma_t; multiply by the pattern value and 1 / voxel volume for the dose).
+ * active_pixels as in tvam_forward (NULL: the dense crop order).  All three projector kinds on
+ * index-matched plans with a non-scattering medium; TVAM_ERR_UNSUPPORTED otherwise.
+ */
+int tvam_plan_rays(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
+                   uint32_t seed, float* rays, void* hip_stream);
 
 /* Exact number of DDA voxel visits of one pass (host-synchronous). */
 int tvam_count_visits(tvam_plan* plan, uint32_t spp, uint32_t seed,
