@@ -14,6 +14,7 @@
 //                          optimize.py:316-318).
 // Dot products accumulate in fp64 per thread, then per block, then over a
 // fixed number of blocks in a fixed order (deterministic).
+// tests/test_gpu_vec_kernels.py pins the dots layout, the fp64 accumulation and that determinism.
 #include "tvam_internal.h"
 
 #define TVAM_VB 256       // threads per block

@@ -363,6 +363,8 @@ int tvam_plan_path(const tvam_plan* plan);
  *   (tvam_lbfgs_armijo's output), so the update follows the probes on the stream
  *   without a host round trip; s_out (may be NULL, no alias of p / d / out) =
  *   out - p, the next step's s_new.  (Both ABI v12.)
+ * Pinned by tests/test_gpu_vec_kernels.py: the dots layout above, f64 accumulation of the exact f32
+ *   products (error <= n 2^-53 sum|product|), and bit-identical dots for identical calls.
  */
 #define TVAM_LBFGS_WORK_DOUBLES (2048 * 64)
 int tvam_lbfgs_history(uint64_t n, const float* p, const float* p_old, const float* g, const float* g_old,

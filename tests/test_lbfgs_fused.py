@@ -2,7 +2,8 @@
 two-loop recursion) against the torch LinearLBFGS restatement of
 lbfgs.py:146-275, on CPU: the three libtvam vector kernels are replaced by a
 numpy stand-in reading the same pointers (the GPU kernels themselves are
-checked in tests/test_gpu_lbfgs.py)."""
+checked in tests/test_gpu_lbfgs.py and, against float64 ground truth, in
+tests/test_gpu_vec_kernels.py)."""
 import ctypes
 
 import numpy as np
