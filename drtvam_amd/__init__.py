@@ -11,6 +11,7 @@ from .film import VolumetricFilm
 from .geometry import Container, IndexMatchedVial, CylindricalVial, SquareVial, CustomVial, DoubleCylindricalVial
 from .integrators import VolumeIntegrator, TVAMIntegrator
 from .lbfgs import LinearLBFGS
+from .optimizers import SGD, Adam
 from .loss import Loss, L2Loss, ThresholdedLoss
 from .motion import Motion, CircularMotion
 from .projector import TVAMProjector, CollimatedProjector, TelecentricProjector, LensProjector

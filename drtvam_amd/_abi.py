@@ -153,6 +153,14 @@ EXPORTS = {
     "tvam_axpy_clamp_dev": (ctypes.c_int, [ctypes.c_uint64, _P, _P, _P, ctypes.c_float, _P, _P, _P]),
     "tvam_lbfgs_armijo": (ctypes.c_int, [ctypes.c_int32, ctypes.c_double, _P, _P, ctypes.c_double, ctypes.c_double,
                                          _P, ctypes.c_double, _P, _P, _P]),
+    "tvam_sgd_step": (ctypes.c_int, [ctypes.c_uint64, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                     ctypes.c_float, _P]),
+    "tvam_adam_step": (ctypes.c_int, [ctypes.c_uint64, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_float, _P]),
+    "tvam_adam_moments": (ctypes.c_int, [ctypes.c_uint64, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_int32, _P, _P, _P]),
+    "tvam_adam_apply": (ctypes.c_int, [ctypes.c_uint64, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_int32, ctypes.c_float, _P]),
     "tvam_row_slices": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P]),
     "tvam_plan_path": (ctypes.c_int, [_P]),
     "tvam_adjoint_slices": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

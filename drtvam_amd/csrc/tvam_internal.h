@@ -345,3 +345,13 @@ hipError_t tvam_launch_axpy_clamp(uint64_t n, const float* p, float alpha, const
 hipError_t tvam_launch_armijo(int nprobe, double a0, const double* probes, const double* loss_dev, double loss_host,
                               double loss_div, const double* gdz, double c1, float* alpha, double* report,
                               hipStream_t stream);
+// First-order optimiser updates (tvam_vec.hip); the scalars already rounded to fp32 (c = fl32(1 - beta)).
+hipError_t tvam_launch_sgd_step(uint64_t n, float* p, const float* g, float* s, float lr, float mu, bool mask,
+                                float lo, hipStream_t stream);
+hipError_t tvam_launch_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1,
+                                 float c1, float b2, float c2, float eps, bool mask, float lo, hipStream_t stream);
+hipError_t tvam_launch_adam_moments(uint64_t n, const float* g, float* m, float* v, float b1, float c1, float b2,
+                                    float c2, bool mask, double* work, double* S, hipStream_t stream);
+hipError_t tvam_launch_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
+                                  const double* count, float lr_t, float eps, bool mask, float lo,
+                                  hipStream_t stream);

@@ -2301,6 +2301,46 @@ extern "C" int tvam_lbfgs_armijo(int32_t nprobe, double alpha0, const double* pr
     return e == hipSuccess ? 0 : hip_fail(e, "armijo launch");
 }
 
+// First-order optimiser updates.  The hyper-parameters arrive as doubles and are rounded here:
+// lr, beta and epsilon to fp32, 1 - beta in double and then to fp32.
+extern "C" int tvam_sgd_step(uint64_t n, float* p, const float* g, float* s, double lr, double momentum, int32_t mask,
+                             float lo, void* stream) {
+    if (!p || !g) return fail(TVAM_ERR_INVALID, "tvam_sgd_step: null argument");
+    if (!s && momentum != 0.0) return fail(TVAM_ERR_INVALID, "tvam_sgd_step: momentum needs the state vector s");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_sgd_step(n, p, g, s, (float)lr, (float)momentum, mask != 0, lo, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "sgd step launch");
+}
+
+extern "C" int tvam_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta_1,
+                              double beta_2, double epsilon, int32_t mask, float lo, void* stream) {
+    if (!p || !g || !m || !v) return fail(TVAM_ERR_INVALID, "tvam_adam_step: null argument");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_adam_step(n, p, g, m, v, (float)lr_t, (float)beta_1, (float)(1.0 - beta_1),
+                                         (float)beta_2, (float)(1.0 - beta_2), (float)epsilon, mask != 0, lo,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "adam step launch");
+}
+
+extern "C" int tvam_adam_moments(uint64_t n, const float* g, float* m, float* v, double beta_1, double beta_2,
+                                 int32_t mask, double* work, double* S, void* stream) {
+    if (!g || !m || !v || !work || !S) return fail(TVAM_ERR_INVALID, "tvam_adam_moments: null argument");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_adam_moments(n, g, m, v, (float)beta_1, (float)(1.0 - beta_1), (float)beta_2,
+                                            (float)(1.0 - beta_2), mask != 0, work, S, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "adam moments launch");
+}
+
+extern "C" int tvam_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
+                               const double* count, double lr_t, double epsilon, int32_t mask, float lo,
+                               void* stream) {
+    if (!p || !m || !S || !count || (mask && !g)) return fail(TVAM_ERR_INVALID, "tvam_adam_apply: null argument");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_adam_apply(n, p, g, m, S, count, (float)lr_t, (float)epsilon, mask != 0, lo,
+                                          (hipStream_t)stream);
+    return e == hipSuccess ? 0 : hip_fail(e, "adam apply launch");
+}
+
 extern "C" int tvam_row_slices(const tvam_desc* desc, int32_t* slice_of_row) {
     if (!desc || !slice_of_row) return fail(TVAM_ERR_INVALID, "null argument");
     int rc = validate(*desc);

@@ -15,6 +15,8 @@
 // Dot products accumulate in fp64 per thread, then per block, then over a
 // fixed number of blocks in a fixed order (deterministic).
 // tests/test_gpu_vec_kernels.py pins the dots layout, the fp64 accumulation and that determinism.
+// The update passes of the first-order optimisers (SGD, Adam; the config's 'optimizer' entry) are
+// at the end of the file: tvam_optim_kernel.
 #include "tvam_internal.h"
 
 #define TVAM_VB 256       // threads per block
@@ -549,4 +551,174 @@ hipError_t tvam_launch_armijo(int nprobe, double a0, const double* probes, const
     hipLaunchKernelGGL(tvam_armijo_kernel, dim3(1), dim3(64), 0, stream, nprobe, a0, probes, loss_dev, loss_host,
                        loss_div, gdz, c1, alpha, report);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// First-order optimisers (drtvam_amd/optimizers.py: Mitsuba's mi.ad.SGD / mi.ad.Adam for one
+// parameter and a scalar learning rate), one fused pass over the pattern vector with the loop's
+// clamp folded in.  Per element, every operation a separate once-rounded fp32 operation in this
+// order (no contraction), keep = mask && g == 0:
+//   SGD       w = p - lr g
+//   SGDM      s' = mu s + g; w = p - lr s'; keep: s' = s
+//   ADAM      m' = b1 m + c1 g; v' = b2 v + c2 (g g); keep: m' = m, v' = v;
+//             den = sqrt(v') + e; w = p - (lr_t m') / den
+//   MOMENTS   ADAM's m', v' only, and S = sum v' (fp64: per thread, per block, then
+//             tvam_partials_kernel over the blocks in block order)
+//   APPLY     den = fl32(sqrt(S / N)) + e (fp64 quotient and root, S and N from device memory);
+//             w = p - (lr_t m') / den
+//   all       keep: w = p; p' = w < lo ? lo : w
+// p, s, m, v are updated in place.  A float4 main path from the 16-byte grid on, a scalar head up
+// to it and a scalar tail; vectors that do not share one offset from that grid go through the
+// scalar path whole.  tests/test_gpu_optimizers.py pins every output to the fp32 model of
+// tests/optim_model.py bit for bit.
+enum { TVAM_OPT_SGD, TVAM_OPT_SGDM, TVAM_OPT_ADAM, TVAM_OPT_MOMENTS, TVAM_OPT_APPLY };
+#define TVAM_OPT_GRID 2048
+
+struct OptimArgs {
+    uint64_t n, head;  // head: leading entries of the scalar path
+    float* p;
+    const float* g;
+    float* a;  // s | m
+    float* b;  // v
+    float lr, k1, c1, k2, c2, eps, lo;
+    const double* S;
+    const double* count;
+    double* work;
+};
+
+template <int KIND, bool MASK>
+__device__ __forceinline__ void optim_elem(float& p, float g, float& a, float& b, const OptimArgs& q, float den_u,
+                                           double& acc) {
+#pragma clang fp contract(off)
+    const bool keep = MASK && g == 0.0f;
+    float w;
+    if (KIND == TVAM_OPT_SGD) {
+        w = p - q.lr * g;
+    } else if (KIND == TVAM_OPT_SGDM) {
+        const float s1 = q.k1 * a + g;
+        w = p - q.lr * s1;
+        if (!keep) a = s1;
+    } else {
+        float den = den_u;
+        if (KIND != TVAM_OPT_APPLY) {
+            const float m1 = q.k1 * a + q.c1 * g;
+            const float v1 = q.k2 * b + q.c2 * (g * g);
+            if (!keep) {
+                a = m1;
+                b = v1;
+            }
+            den = __builtin_sqrtf(b) + q.eps;
+        }
+        if (KIND == TVAM_OPT_MOMENTS) {
+            acc += (double)b;
+            return;
+        }
+        w = p - (q.lr * a) / den;
+    }
+    if (keep) w = p;
+    p = w < q.lo ? q.lo : w;
+}
+
+template <int KIND, bool MASK>
+__global__ __launch_bounds__(TVAM_VB) void tvam_optim_kernel(OptimArgs q) {
+    constexpr bool HP = KIND != TVAM_OPT_MOMENTS;            // p read and written
+    constexpr bool HG = KIND != TVAM_OPT_APPLY || MASK;      // g read
+    constexpr bool HA = KIND != TVAM_OPT_SGD;                // s | m read
+    constexpr bool WA = HA && KIND != TVAM_OPT_APPLY;        //       and written
+    constexpr bool HB = KIND == TVAM_OPT_ADAM || KIND == TVAM_OPT_MOMENTS;  // v read and written
+    float den_u = 0.0f;
+    if (KIND == TVAM_OPT_APPLY) den_u = (float)sqrt(q.S[0] / q.count[0]) + q.eps;
+    double acc[1] = {0.0};
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    auto scalar = [&](uint64_t i) {
+        float p = 0.0f, g = 0.0f, a = 0.0f, b = 0.0f;
+        if (HP) p = q.p[i];
+        if (HG) g = q.g[i];
+        if (HA) a = q.a[i];
+        if (HB) b = q.b[i];
+        optim_elem<KIND, MASK>(p, g, a, b, q, den_u, acc[0]);
+        if (HP) q.p[i] = p;
+        if (WA) q.a[i] = a;
+        if (HB) q.b[i] = b;
+    };
+    for (uint64_t i = tid; i < q.head; i += stride) scalar(i);
+    const uint64_t n4 = (q.n - q.head) / 4;
+    for (uint64_t i = tid; i < n4; i += stride) {
+        const float4 z = make_float4(0, 0, 0, 0);
+        float4 p4 = z, g4 = z, a4 = z, b4 = z;
+        if (HP) p4 = vld(q.p + q.head, i);
+        if (HG) g4 = vld(q.g + q.head, i);
+        if (HA) a4 = vld(q.a + q.head, i);
+        if (HB) b4 = vld(q.b + q.head, i);
+        optim_elem<KIND, MASK>(p4.x, g4.x, a4.x, b4.x, q, den_u, acc[0]);
+        optim_elem<KIND, MASK>(p4.y, g4.y, a4.y, b4.y, q, den_u, acc[0]);
+        optim_elem<KIND, MASK>(p4.z, g4.z, a4.z, b4.z, q, den_u, acc[0]);
+        optim_elem<KIND, MASK>(p4.w, g4.w, a4.w, b4.w, q, den_u, acc[0]);
+        if (HP) reinterpret_cast<float4*>(q.p + q.head)[i] = p4;
+        if (WA) reinterpret_cast<float4*>(q.a + q.head)[i] = a4;
+        if (HB) reinterpret_cast<float4*>(q.b + q.head)[i] = b4;
+    }
+    for (uint64_t i = q.head + 4 * n4 + tid; i < q.n; i += stride) scalar(i);
+    if constexpr (KIND == TVAM_OPT_MOMENTS) block_partials<1>(acc, q.work);
+}
+
+// Entries up to the 16-byte grid when every vector in use sits at the same offset from it, else all n.
+static uint64_t optim_head(uint64_t n, const void* const* v, int nv) {
+    uintptr_t off = 0;
+    bool first = true;
+    for (int j = 0; j < nv; ++j) {
+        if (!v[j]) continue;
+        const uintptr_t o = (uintptr_t)v[j] & 15u;
+        if (first) off = o;
+        else if (o != off) return n;
+        first = false;
+    }
+    if (off & 3u) return n;
+    return std::min<uint64_t>(n, ((16u - off) & 15u) / 4);
+}
+
+template <int KIND>
+static hipError_t launch_optim(bool mask, OptimArgs q, double* S_out, hipStream_t stream) {
+    const void* v[4] = {q.p, q.g, q.a, q.b};
+    q.head = optim_head(q.n, v, 4);
+    const dim3 grid(TVAM_OPT_GRID), block(TVAM_VB);
+    if (mask)
+        hipLaunchKernelGGL((tvam_optim_kernel<KIND, true>), grid, block, 0, stream, q);
+    else
+        hipLaunchKernelGGL((tvam_optim_kernel<KIND, false>), grid, block, 0, stream, q);
+    if (KIND == TVAM_OPT_MOMENTS)
+        hipLaunchKernelGGL(tvam_partials_kernel, dim3(1), dim3(TVAM_VB), 0, stream, 1, TVAM_OPT_GRID, q.work, S_out);
+    return hipGetLastError();
+}
+
+hipError_t tvam_launch_sgd_step(uint64_t n, float* p, const float* g, float* s, float lr, float mu, bool mask,
+                                float lo, hipStream_t stream) {
+    OptimArgs q{};
+    q.n = n, q.p = p, q.g = g, q.a = s, q.lr = lr, q.k1 = mu, q.lo = lo;
+    return s ? launch_optim<TVAM_OPT_SGDM>(mask, q, nullptr, stream) : launch_optim<TVAM_OPT_SGD>(mask, q, nullptr, stream);
+}
+
+hipError_t tvam_launch_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1,
+                                 float c1, float b2, float c2, float eps, bool mask, float lo, hipStream_t stream) {
+    OptimArgs q{};
+    q.n = n, q.p = p, q.g = g, q.a = m, q.b = v, q.lr = lr_t, q.k1 = b1, q.c1 = c1, q.k2 = b2, q.c2 = c2;
+    q.eps = eps, q.lo = lo;
+    return launch_optim<TVAM_OPT_ADAM>(mask, q, nullptr, stream);
+}
+
+hipError_t tvam_launch_adam_moments(uint64_t n, const float* g, float* m, float* v, float b1, float c1, float b2,
+                                    float c2, bool mask, double* work, double* S, hipStream_t stream) {
+    OptimArgs q{};
+    q.n = n, q.g = g, q.a = m, q.b = v, q.k1 = b1, q.c1 = c1, q.k2 = b2, q.c2 = c2, q.work = work;
+    return launch_optim<TVAM_OPT_MOMENTS>(mask, q, S, stream);
+}
+
+hipError_t tvam_launch_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
+                                  const double* count, float lr_t, float eps, bool mask, float lo,
+                                  hipStream_t stream) {
+    OptimArgs q{};
+    q.n = n, q.p = p, q.g = mask ? g : nullptr, q.a = const_cast<float*>(m), q.S = S, q.count = count;
+    q.lr = lr_t, q.eps = eps, q.lo = lo;
+    return launch_optim<TVAM_OPT_APPLY>(mask, q, nullptr, stream);
 }

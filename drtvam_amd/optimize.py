@@ -15,6 +15,10 @@ autograd with the same render op.  Under torch.distributed the projector
 angles are sharded across ranks: each rank renders its angles, the partial
 dose is all-reduced (RCCL), the adjoint is rank-local and L-BFGS dots are
 all-reduced scalars.
+
+The config's 'optimizer' entry picks the optimiser as optimize.py:203-225 does: 'adam' and 'sgd'
+build drtvam_amd.optimizers.Adam / SGD from the remaining keys (one forward, loss, adjoint and
+one fused update + clamp pass per iteration); any other type, or no entry, is the L-BFGS.
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ from .geometry import geometries
 from .integrators import VolumeIntegrator
 from .lbfgs import DirectionPipeline, FusedLinearLBFGS, LinearLBFGS
 from .loss import losses, ThresholdedLoss
+from .optimizers import Adam, SGD
 from .scene import load_dict
 from .utils import discretize, analytic_target, mesh_bbox, target_transform, save_vol, save_img
 
@@ -288,8 +293,21 @@ class ShardedLoop:
         return v if s is None else v + s
 
     # ---- optimisation -------------------------------------------------------------
+    optimizer_cfg = None  # the config's 'optimizer' entry: {'type': 'adam' | 'sgd' | anything else (L-BFGS), ...}
+
     def make_optimizer(self):
         key = 'projector.active_data'
+        cfg = dict(self.optimizer_cfg or {'type': 'lbfgs'})
+        otype = cfg.pop('type', 'lbfgs')
+        if otype in ('adam', 'sgd'):
+            # mi.ad.Adam(**rest) / mi.ad.SGD(**rest) (optimize.py:207-211), the loop's clamp at 0
+            # (optimize.py:320) fused into the update; uniform's sum runs over every rank's entries
+            if otype == 'adam' and cfg.get('uniform', False):
+                cfg.update(allreduce=self.allreduce_ if self.dist is not None else None, count=self.n_active_global())
+            opt = (Adam if otype == 'adam' else SGD)(lo=0.0, **cfg)
+            opt[key] = self.x0
+            self.opt = opt
+            return opt
 
         def render_fn(vars_):
             return self.forward(vars_[key], self._seed)
@@ -316,6 +334,8 @@ class ShardedLoop:
         key = 'projector.active_data'
         self._seed = i
         x = self.opt[key]
+        if isinstance(self.opt, (Adam, SGD)):
+            return self._iteration_first_order(x, i)
         if isinstance(self.opt, FusedLinearLBFGS) and self.fused and self.opt.pipeline is not None:
             loss_v = self._iteration_pipelined(x, i)
             self.loss_hist.append(loss_v)
@@ -348,6 +368,24 @@ class ShardedLoop:
         if getattr(self.opt, 'clamp_min', None) != 0.0:  # the fused optimizer clamps in its update pass
             with torch.no_grad():
                 self.opt[key] = torch.clamp_min(self.opt[key].detach(), 0.0)
+        return loss_v
+
+    def _iteration_first_order(self, x, i):
+        """iteration() with Adam / SGD (optimize.py:292-320): one forward, the loss and dL/dvol, the
+        host read of the loss, the adjoint (+ the sparsity gradient) and one update pass, which
+        clamps at 0 itself.  No search direction: no second forward."""
+        vol = self.forward(x, i)
+        loss, gvol = self.loss_value_grad(vol, x)
+        loss_v = float(loss)  # host sync, optimize.py:303
+        self.loss_hist.append(loss_v)
+        g = self.adjoint(gvol, i)
+        sg = self.sparsity_grad(x)
+        if sg is not None:
+            g = g + sg
+        x.grad = g
+        if loss_v == 0.0:
+            return loss_v
+        self.opt.step()
         return loss_v
 
     def _iteration_pipelined(self, x, i):
@@ -460,8 +498,11 @@ class TvamProblem(ShardedLoop):
         self.transmission_only = config.get('transmission_only', True)
         self.regular_sampling = config.get('regular_sampling', False)
         self.n_steps = config.get('n_steps', 40)
+        # 'adam' / 'sgd': the first-order optimisers, built from the remaining keys; any other type
+        # (or no entry) is the linear L-BFGS, which ignores further keys (optimize.py:203-222)
+        self.optimizer_cfg = dict(config.get('optimizer', {'type': 'lbfgs'}))
 
-        lcfg = dict(config.get('loss', {'type': 'threshold'}))
+        lcfg =dict(config.get('loss', {'type': 'threshold'}))
         ltype = lcfg.pop('type', 'threshold')
         if ltype not in losses:
             raise ValueError(f"Unknown loss type: '{ltype}'. Available losses are: {list(losses.keys())}")
@@ -762,6 +803,8 @@ class TvamProblem(ShardedLoop):
 
 def optimize(config, patterns_fwd=None, device=None):
     """Optimise the patterns (optimize.py:81-368).  Returns the final dose volume."""
+    if 'optimizer' not in config:
+        print("No optimizer specified. Using linear L-BFGS.")
     prob = TvamProblem(config, device=device, filter_pixels=patterns_fwd is None)
     output = config.get('output', '.')
     os.makedirs(output, exist_ok=True)
@@ -902,7 +945,7 @@ def apply_overrides(config, overrides):
         key = key.split('.')
         tmp = config
         for k in key[:-1]:
-            tmp = tmp[k]
+            tmp = tmp.setdefault(k, {})  # e.g. -D optimizer.type=adam on a config without the entry
         tmp[key[-1]] = value
     return config
 

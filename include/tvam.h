@@ -391,6 +391,40 @@ int tvam_lbfgs_armijo(int32_t nprobe, double alpha0, const double* probes, const
                       double loss_div, const double* gdz, double c1, float* alpha, double* report,
                       void* hip_stream);
 
+/*
+ * First-order optimiser updates (Mitsuba's mi.ad.SGD / mi.ad.Adam for one parameter and a scalar
+ * learning rate; drtvam_amd/optimizers.py), fused with the loop's clamp (optimize.py:320).  All
+ * vectors are f32, n entries, updated in place; any 4-byte alignment is accepted (vectors sharing
+ * one offset from the 16-byte grid take the float4 path).  Hyper-parameters arrive as doubles and
+ * are rounded inside: lr32 = fl32(lr), mu = fl32(momentum), b = fl32(beta), c = fl32(1 - beta)
+ * with the subtraction in double, e = fl32(epsilon).  Per element every operation is one
+ * once-rounded f32 operation in the written order (no fma); keep = mask && g == 0:
+ * tvam_sgd_step: s == NULL (momentum must be 0): w = p - lr32 g.  Else s' = mu s + g;
+ *   w = p - lr32 s'; keep: s' = s.  Then keep: w = p; p' = w < lo ? lo : w.
+ * tvam_adam_step: m' = b1 m + c1 g; v' = b2 v + c2 (g g); keep: m' = m, v' = v;
+ *   den = sqrt(v') + e; w = p - (lr_t m') / den; keep: w = p; p' = w < lo ? lo : w.
+ *   lr_t = fl32(fl32(lr) fl32(sqrt(1 - beta_2^t) / (1 - beta_1^t))) is the caller's, for its step
+ *   count t.
+ * tvam_adam_moments / tvam_adam_apply: Adam with uniform = True in two passes.  The moments pass
+ *   updates m and v as above and writes S[0] (device f64) = sum v', accumulated in f64 per thread,
+ *   per block, then over the blocks in block order (deterministic); work: >=
+ *   TVAM_LBFGS_WORK_DOUBLES f64 of scratch.  The caller may all-reduce S.  The apply pass reads
+ *   S[0] and count[0] (device f64: the entries of all ranks) and takes den = fl32(sqrt(S / count))
+ *   + e (quotient and root in f64) for every element; g is read only with mask (else may be
+ *   NULL).  No host round trip between the two.
+ * n == 0 returns 0 without a launch; a NULL required pointer returns TVAM_ERR_INVALID.
+ * Pinned by tests/test_gpu_optimizers.py: p, s, m, v bit for bit against the f32 model of
+ *   tests/optim_model.py, S within n 2^-53 sum|v'| and bit-identical for identical calls.
+ */
+int tvam_sgd_step(uint64_t n, float* p, const float* g, float* s, double lr, double momentum, int32_t mask,
+                  float lo, void* hip_stream);
+int tvam_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta_1,
+                   double beta_2, double epsilon, int32_t mask, float lo, void* hip_stream);
+int tvam_adam_moments(uint64_t n, const float* g, float* m, float* v, double beta_1, double beta_2, int32_t mask,
+                      double* work, double* S, void* hip_stream);
+int tvam_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S, const double* count,
+                    double lr_t, double epsilon, int32_t mask, float lo, void* hip_stream);
+
 /* Global film z-slice of every crop row's rays under regular sampling
    (slice_of_row[crop_y]; -1 when the row's rays miss the grid or the vial),
    computed with the plan's own fp32 ray generation: the row <-> slice map
