@@ -170,6 +170,7 @@ EXPORTS = {
     "tvam_compute_volume": (ctypes.c_int, [_P, ctypes.c_uint32, _P, _P]),
     "tvam_plan_set_volumes": (ctypes.c_int, [_P, _P]),
     "tvam_radon": (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _P, _P]),
+    "tvam_corner": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
     "tvam_plan_rays": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_count_visits": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
     "tvam_plan_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64)]),

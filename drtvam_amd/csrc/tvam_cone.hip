@@ -18,126 +18,18 @@
 
 #include <algorithm>
 
-#include "tvam_seg3d.h"
+#include "tvam_cone_ray.h"
 
 namespace {
 
-struct ConeRay {
-    float o[3], d[3];  // world-space projector ray
-    float o2[3];       // medium segment (o2, d, [0, maxt])
-    float maxt;
-};
-
-// Mitsuba warp::square_to_uniform_disk_concentric (Shirley & Chiu), restated
-__device__ __forceinline__ void cn_disk(float u1, float u2, float& x, float& y) {
-    const float sx = 2.0f * u1 - 1.0f, sy = 2.0f * u2 - 1.0f;
-    const bool q = fabsf(sx) < fabsf(sy);
-    const float r = q ? sy : sx, rp = q ? sx : sy;
-    float phi = 0.78539816339744830962f * rp / r;
-    if (q) phi = 1.57079632679489661923f - phi;
-    if (sx == 0.0f && sy == 0.0f) phi = 0.0f;
-    x = r * cosf(phi);
-    y = r * sinf(phi);
-}
-
-// Index-matched vial, 3-D ray (Mitsuba's open cylinder with a null BSDF, volume.py:191-216):
-// the first tube hit is the entry only when it is front-facing (else the ray came in through an
-// open end and never enters the medium through the interface: no deposit); o2 is the hit offset
-// inward by spawn_ray's (1 + max|p|) eps (or_segment_index_matched's rule); the segment ends at
-// the next tube hit from o2, and a ray that leaves through an open end has no valid si there
-// (volume.py:268): no deposit either.
-__device__ __forceinline__ bool cn_segment(const TvamConsts& k, ConeRay& r) {
-    const float t0 = sc_tube_hit(r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.d[2], k.vial_r, k.vial_half_h);
-    if (!(t0 < TVAM_INF)) return false;
-    const float px = fmaf(r.d[0], t0, r.o[0]), py = fmaf(r.d[1], t0, r.o[1]), pz = fmaf(r.d[2], t0, r.o[2]);
-    const float rp = sqrtf(px * px + py * py);
-    const float nx = px / rp, ny = py / rp;
-    const float ndd = nx * r.d[0] + ny * r.d[1] + 0.0f * r.d[2];
-    if (!(ndd < 0.0f)) return false;
-    const float m = fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
-    const float mag = -((1.0f + m) * TVAM_RAY_EPS);
-    r.o2[0] = fmaf(mag, nx, px);
-    r.o2[1] = fmaf(mag, ny, py);
-    r.o2[2] = pz;
-    const float t1 = sc_tube_hit(r.o2[0], r.o2[1], r.o2[2], r.d[0], r.d[1], r.d[2], k.vial_r, k.vial_half_h);
-    if (!(t1 < TVAM_INF)) return false;
-    r.maxt = t1;
-    return true;
-}
-
-// The ray of dense shard entry `local`, sample `smp`, and its medium segment.  Returns whether it
-// deposits.  The collimated projector takes tvam_ray_world / tvam_segment_im (the ray records'
-// own expressions), so that the export of such a plan is the oracle's ray bit for bit.
+// The ray of dense shard entry `local`, sample `smp` (cn_ray_at, tvam_cone_ray.h).
 __device__ __forceinline__ bool cn_ray(const TvamConsts& k, const TvamTiles& tp, const int32_t* idxmap, int64_t local,
                                        int smp, ConeRay& r) {
     const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
     const int al = (int)(local / per_angle);
     const int64_t pix = local - (int64_t)al * per_angle;
     const int rowc = (int)(pix / k.crop_x), colc = (int)(pix - (int64_t)rowc * k.crop_x);
-    TvamPcg rng;
-    rng.seed(tp.seed, tvam_stream(k, idxmap, local, tp.spp, smp));
-    float jx = 0.5f, jy = 0.5f;
-    if (!k.regular) {
-        jx = rng.next_float();
-        jy = rng.next_float();
-    }
-    float c, sn;
-    if (k.sample_time) {  // common.py:101-104: time = (angle + u) / n_patterns
-        float time = (float)(k.a0 + al);
-        time = time + rng.next_float();
-        time = time / (float)k.n_patterns;
-        float alpha = TVAM_TWO_PI * time;
-        if (k.clockwise) alpha = -alpha;
-        c = cosf(alpha);
-        sn = sinf(alpha);
-    } else {
-        const float2 csv = tp.cs[al];
-        c = csv.x;
-        sn = csv.y;
-    }
-    const float u1 = rng.next_float(), u2 = rng.next_float();  // aperture sample (projector.py:160)
-    float xc, yc;
-    tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
-    if (k.proj_type == TVAM_PROJECTOR_COLLIMATED) {
-        tvam_ray_world(k, c, sn, xc, yc, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1]);
-        r.d[2] = 0.0f;
-        r.o2[2] = r.o[2];
-        return tvam_segment_im(k, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.o2[0], r.o2[1], r.maxt);
-    }
-    float ax, ay;
-    cn_disk(u1, u2, ax, ay);
-    ax = k.ap_r * ax;
-    ay = k.ap_r * ay;
-    // camera space: origin (X, Y, 0) on the aperture plane, direction towards the pixel's point of
-    // the focus plane
-    float X, Y, vx, vy, vz;
-    if (k.proj_type == TVAM_PROJECTOR_TELECENTRIC) {  // projector.py:220-234
-        X = xc + ax;
-        Y = yc + ay;
-        vx = -ax;
-        vy = -ay;
-        vz = 0.005f + k.focus;  // the pixel's point sits on the near plane z_c = 0.005
-    } else {  // projector.py:273-286: focus_p = near_p (focus_distance / near_p.z) = (xc, yc, focus)
-        X = ax;
-        Y = ay;
-        vx = xc - ax;
-        vy = yc - ay;
-        vz = k.focus;
-    }
-    const float inv = 1.0f / sqrtf(vx * vx + vy * vy + vz * vz);
-    vx = vx * inv;
-    vy = vy * inv;
-    vz = vz * inv;
-    // to_world (motion.py:26-36; tvam_ray_world with a general camera point and direction):
-    // (X, Y, Z) -> (c (D - Z) + s X, s (D - Z) - c X, Y), Z = 0
-    const float D = k.dist;
-    r.o[0] = c * D + sn * X;
-    r.o[1] = sn * D - c * X;
-    r.o[2] = Y;
-    r.d[0] = sn * vx - c * vz;
-    r.d[1] = -sn * vz - c * vx;
-    r.d[2] = vy;
-    return cn_segment(k, r);
+    return cn_ray_at(k, tp, al, colc, rowc, tvam_stream(k, idxmap, local, tp.spp, smp), r);
 }
 
 // The segment's DDA (sensor.py:327-438), stepped like the oracle's or_dda op for op in fp32: the

@@ -301,6 +301,11 @@ hipError_t tvam_launch_discretize(const TvamConsts& k, const float* h_tris, floa
 hipError_t tvam_launch_radon(const TvamConsts& k, const TvamTiles& t, const float* tgt, int ntgt, int max_depth,
                              float wray, float* radon, hipStream_t stream);
 
+// Corner filter (tvam_corner.hip): keep[n] (1 / 0) and, when non-null, hits[n][4] = {p, t} of the
+// first surface each active entry's ray meets.  k: regular = 1, sample_time = 0; t: seed 0, spp 1.
+hipError_t tvam_launch_corner(const TvamConsts& k, const TvamTiles& t, const uint32_t* active, int64_t n, float dist,
+                              float radius, float* keep, float* hits, hipStream_t stream);
+
 // Per-ray pre-pass: ray generation, vial segment and DDA initialisation of
 // every ray of the shard, stored as the records the tile kernels resume from.
 hipError_t tvam_launch_stray_lists(const TvamConsts& k, const TvamTiles& t, hipStream_t stream);

@@ -1956,6 +1956,33 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
     return e == hipSuccess ? 0 : hip_fail(e, "radon launch");
 }
 
+// 'filter_corner' (tvam_corner.hip): reads only the projector, motion, vial and occluder fields, so
+// every plan kind serves it (an `empty` plan too: the pass does not depend on max_depth).
+extern "C" int tvam_corner(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, float dist, float radius,
+                           float* keep, float* hits, void* stream_) {
+    if (!p) return fail(TVAM_ERR_INVALID, "tvam_corner: null plan");
+    if (!keep) return fail(TVAM_ERR_INVALID, "tvam_corner: null keep");
+    if (!(radius >= 0.0f)) return fail(TVAM_ERR_INVALID, "tvam_corner: radius must be >= 0");
+    if (!std::isfinite(dist)) return fail(TVAM_ERR_INVALID, "tvam_corner: dist must be finite");
+    if (((uintptr_t)hits & 15u) != 0) return fail(TVAM_ERR_INVALID, "tvam_corner: hits must be 16-byte aligned");
+    const tvam_desc& d = p->desc;
+    const uint64_t dense_n = (uint64_t)(p->k.a1 - p->k.a0) * d.crop_y * d.crop_x;
+    if (!active_pixels && n_active != dense_n)
+        return fail(TVAM_ERR_INVALID, "tvam_corner: n_active must equal the shard's dense size when active_pixels is null");
+    if (n_active > (uint64_t)INT64_MAX) return fail(TVAM_ERR_INVALID, "tvam_corner: n_active too large");
+    if (n_active == 0) return 0;
+    hipError_t e = hipSetDevice(p->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    TvamConsts k = p->k;  // the pass's own sampling (optimize.py:167-171): regular, spp 1, seed 0, no time sample
+    k.regular = 1;
+    k.sample_time = 0;
+    TvamTiles t = p->tiles;
+    t.spp = 1;
+    t.seed = 0;
+    e = tvam_launch_corner(k, t, active_pixels, (int64_t)n_active, dist, radius, keep, hits, (hipStream_t)stream_);
+    return e == hipSuccess ? 0 : hip_fail(e, "corner launch");
+}
+
 extern "C" int tvam_compute_volume(tvam_plan* p, uint32_t sample_count, float* volumes, void* stream_) {
     if (!p || !volumes) return fail(TVAM_ERR_INVALID, "null argument");
     if (!p->surface) return fail(TVAM_ERR_INVALID, "compute_volume needs a surface-aware film (film_channels 2)");

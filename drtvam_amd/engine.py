@@ -190,6 +190,27 @@ class Projection:
                                            seed & 0xFFFFFFFF, max_depth, out.data_ptr(), _stream_ptr(self.device)))
         return out
 
+    def corner(self, dist: float, radius: float = 0.1, active_pixels: Optional[torch.Tensor] = None,
+               n_active: Optional[int] = None, hits: bool = False):
+        """Corner filter mask of the active entries (tvam_corner; filter_corner.py:17-66): float32
+        1 where the ray through the pixel's centre meets the scene's first surface at p and not
+        sqrt((|p.x| - dist)^2 + (|p.y| - dist)^2) < radius, else 0.  active_pixels: int32 full-DMD
+        indices (None: this plan's dense shard order).  With hits=True returns (keep, hits), hits
+        [n, 4] = p.x, p.y, p.z, t (t = -1 on a miss)."""
+        if active_pixels is not None:
+            self._check_tensor(active_pixels, torch.int32, "active_pixels")
+            n_active = int(active_pixels.numel())
+        elif n_active is None:
+            a0, a1 = self.desc.angle_begin, (self.desc.angle_end if self.desc.angle_end >= 0 else self.desc.n_patterns)
+            n_active = (a1 - a0) * self.desc.crop_y * self.desc.crop_x
+        keep = torch.empty(int(n_active), dtype=torch.float32, device=self.device)
+        h = torch.empty((int(n_active), 4), dtype=torch.float32, device=self.device) if hits else None
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_corner(
+                self._plan, None if active_pixels is None else active_pixels.data_ptr(), int(n_active), float(dist),
+                float(radius), keep.data_ptr(), None if h is None else h.data_ptr(), _stream_ptr(self.device)))
+        return (keep, h) if hits else keep
+
     def rays(self, n_active: Optional[int] = None, active_pixels: Optional[torch.Tensor] = None, spp: int = 1,
              seed: int = 0) -> torch.Tensor:
         """The projector rays of a call (tvam_plan_rays), [n_active * spp, 16] float32 in sampler-stream

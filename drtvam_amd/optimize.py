@@ -588,7 +588,7 @@ class TvamProblem(ShardedLoop):
         self.n_global = A * per_angle
         self.n_local = (self.a1 - self.a0) * (self.r1 - self.r0) * self.crop_x
         self.x0 = self.local_from_global(p.active_data)
-        # the dense crop order unless filter_radon compacts the set; the ray weight divides by
+        # the dense crop order unless filter_radon / filter_corner compact the set; the ray weight divides by
         # the whole (all ranks') active set size, as the unsharded reference does
         self.active_pixels = None
         self.active_dense = None
@@ -596,6 +596,8 @@ class TvamProblem(ShardedLoop):
         self.proj = self._active_projection(self.integrator, self.sensor)
         if config.get('filter_radon', False) and filter_pixels:
             self._filter_radon(config)
+        if 'filter_corner' in config and filter_pixels:
+            self._filter_corner(config)
         self.fused = fusable and self.target.shape[-1] == 1
         self.grad_vol = torch.empty(self.proj.film_shape, dtype=torch.float32, device=dev)
         self.opt = None
@@ -619,13 +621,37 @@ class TvamProblem(ShardedLoop):
         radon = Projection(d, self.device).radon(target_triangles(self.scene), spp=config.get('spp_filter_radon', 4),
                                                  seed=0, max_depth=5)
         local = torch.nonzero(radon > 0).reshape(-1)  # dense indices of this rank's shard, ascending
-        counts = [int(local.numel())]
+        self._compact_active(local, "filter_radon", "No active pixels found in the Radon transform.")
+
+    def _filter_corner(self, config):
+        """Deactivate the pixels whose ray misses the scene or enters the vial within `radius` of a
+        corner at (+-dist, +-dist) (optimize.py:166-185): the corner pass (tvam_corner: regular
+        sampling, one sample, seed 0) over this rank's current active entries -- the dense crop
+        order, or filter_radon's survivors, so the two filters intersect -- then the same
+        compaction as filter_radon."""
+        fc = dict(config['filter_corner'])
+        keep = self.proj.corner(fc['dist'], fc.get('radius', 0.1), active_pixels=self.active_pixels,
+                                n_active=self.n_local)
+        self._compact_active(torch.nonzero(keep > 0).reshape(-1), "filter_corner",
+                             "No active pixels left by the corner filter.")
+
+    def _compact_active(self, sel, what, empty_msg):
+        """Keep the entries `sel` (ascending positions in this rank's current active vector) like the
+        reference's dr.compress: active_pixels holds the survivors' full-DMD indices in dense order,
+        the pattern vector restarts from zeros of that length, and the sampler streams follow the
+        position in the whole (all ranks') compacted set."""
+        counts = [int(sel.numel())]
         if self.dist is not None:
             counts = [None] * self.world
-            self.dist.all_gather_object(counts, int(local.numel()))
+            self.dist.all_gather_object(counts, int(sel.numel()))
         self.n_filtered = int(sum(counts))
         if self.n_filtered == 0:
-            raise ValueError("No active pixels found in the Radon transform.")
+            raise ValueError(empty_msg)
+        if self.active_dense is None:
+            local = sel  # dense indices of this rank's shard
+            self.n_dense_local = self.n_local
+        else:
+            local = self.active_dense[sel]
         # full-DMD pixel index of each surviving dense entry [angle][crop row][crop col] of the plan
         pd = self.proj.desc
         cx, cy = int(pd.crop_x), int(pd.crop_y)
@@ -636,10 +662,9 @@ class TvamProblem(ShardedLoop):
         W, H = int(pd.res_x), int(pd.res_y)
         pix = (al + int(pd.angle_begin)) * (W * H) + (row + int(pd.crop_offset_y)) * W + col + int(pd.crop_offset_x)
         if pix.numel() and int(pix.max()) >= 2 ** 31:
-            raise ValueError("filter_radon: DMD pixel index exceeds the int32 active_pixels range")
+            raise ValueError(f"{what}: DMD pixel index exceeds the int32 active_pixels range")
         self.active_pixels = pix.to(torch.int32).contiguous()
         self.active_dense = local  # scatter positions of the compacted vector in this rank's dense layout
-        self.n_dense_local = self.n_local
         self.n_local = int(local.numel())
         # angle shards are contiguous blocks of the global dense order: this rank's first
         # active entry sits after every lower rank's (slab shards interleave, but run only

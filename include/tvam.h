@@ -251,6 +251,29 @@ int tvam_plan_stats(tvam_plan* plan, uint64_t* fallback_tiles);
 int tvam_radon(tvam_plan* plan, const float* target_tris, int32_t n_target_tris, uint32_t spp, uint32_t seed,
                int32_t max_depth, float* radon, void* stream);
 
+/* Corner filter (integrators/filter_corner.py:17-66, optimize.py:166-185, 'filter_corner'): for
+   every active entry, one ray through the centre of its pixel (regular sampling, spp 1, seed 0,
+   no time sample, whatever the plan's own sampling is; 'telecentric' / 'lens' still take the
+   aperture draw of sampler stream = the entry's position in the whole active set, as
+   tvam_plan_set_active places this plan in it) is intersected with the scene's surfaces: the
+   container's outer surface (index_matched: open tube r, cylindrical: open tube r_ext, both
+   |z| <= height / 2 and hit from either side; square: the closed cuboid w_ext x w_ext x height)
+   and the occluder triangles.  The target mesh, which the reference's scene also holds, lies
+   inside the container and is left out.  keep[i] (device, f32, n_active entries, overwritten) =
+   1 when the ray meets a surface at p and not sqrt((|p.x| - dist)^2 + (|p.y| - dist)^2) < radius,
+   else 0.  hits (device, 16-byte aligned, [n_active][4] f32; may be NULL) = {p.x, p.y, p.z, t},
+   {0, 0, 0, -1} on a miss.
+     active_pixels : as in tvam_forward (u32 full-DMD indices), any pixel of the DMD; an entry
+                     whose angle is outside the plan's angle shard is dropped (keep 0, t -1).
+                     NULL: the plan's dense shard order [angle][crop row][crop col] (the row band
+                     of a slab plan), n_active = shard angles * crop_y * crop_x.
+   Asynchronous on hip_stream.  Every plan kind (projector, vial, occluders, scattering, slab or
+   angle shard).  TVAM_ERR_INVALID: null plan / keep, radius < 0, non-finite dist, misaligned
+   hits, n_active != the shard's size with active_pixels == NULL.  (Added to ABI v13: no struct or
+   existing signature changed.) */
+int tvam_corner(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active,
+                float dist, float radius, float* keep, float* hits, void* hip_stream);
+
 /* Surface-aware discretisation (film_channels == 2; VolumetricSensor.compute_volume,
    sensor.py:47-110): volumes[z][y][x][2] (device, f32, overwritten) = the voxel volume
    inside (channel 0) / outside (1) the target mesh, estimated from sample_count points per
