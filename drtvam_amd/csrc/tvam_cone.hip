@@ -22,14 +22,10 @@
 
 namespace {
 
-// The ray of dense shard entry `local`, sample `smp` (cn_ray_at, tvam_cone_ray.h).
-__device__ __forceinline__ bool cn_ray(const TvamConsts& k, const TvamTiles& tp, const int32_t* idxmap, int64_t local,
-                                       int smp, ConeRay& r) {
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
-    const int al = (int)(local / per_angle);
-    const int64_t pix = local - (int64_t)al * per_angle;
-    const int rowc = (int)(pix / k.crop_x), colc = (int)(pix - (int64_t)rowc * k.crop_x);
-    return cn_ray_at(k, tp, al, colc, rowc, tvam_stream(k, idxmap, local, tp.spp, smp), r);
+// The ray of flat index ix (cn_ray_at, tvam_cone_ray.h).
+__device__ __forceinline__ bool cn_ray(const TvamConsts& k, const TvamTiles& tp, const int32_t* idxmap,
+                                       const TvamPathIndex& ix, ConeRay& r) {
+    return cn_ray_at(k, tp, ix.al, ix.colc, ix.rowc, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), r);
 }
 
 // The segment's DDA (sensor.py:327-438), stepped like the oracle's or_dda op for op in fp32: the
@@ -110,31 +106,22 @@ __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles 
     const int spp = (int)tp.spp;
     const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * spp;
     uint64_t nvis = 0;
+    const bool f32 = false;  // (the 64-bit decode alone: the second one costs this kernel its 7th wave/SIMD)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t local = i / spp;
-        const int smp = (int)(i - local * spp);
-        float em = 1.0f;
-        int64_t act = local;
-        if (MODE == TVAM_MODE_FWD) {
-            const float p = pat[local];
-            if (p == 0.0f && k.skip_zero) continue;
-            em = p * k.wscale * k.inv_vol;
-        } else if (idxmap) {
-            act = idxmap[local];
-            if (act < 0) continue;
-        }
+        TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
+        float em;
+        int64_t act;
+        if (!tvam_path_gate<MODE>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+        tvam_path_pixel(k, f32, ix);
         ConeRay r;
-        if (!cn_ray(k, tp, idxmap, local, smp, r)) continue;
+        if (!cn_ray(k, tp, idxmap, ix, r)) continue;
         const float acc = cn_dda<MODE>(k, r.o2, r.d, r.maxt, em, out, gin, nvis);
         if (MODE == TVAM_MODE_ADJ) {
             if (spp == 1) out[act] = acc * k.wscale;  // the entry's only ray: no atomic
             else if (acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
         }
     }
-    if (MODE == TVAM_MODE_COUNT) {
-        for (int off = 32; off > 0; off >>= 1) nvis += __shfl_down(nvis, off, 64);
-        if ((threadIdx.x & 63) == 0 && nvis) atomicAdd(counter, (unsigned long long)nvis);
-    }
+    if (MODE == TVAM_MODE_COUNT) tvam_count_reduce(nvis, counter);
 }
 
 // One brick-bin record per ray of paths [sb.p0, sb.p1) (sb.slots = 1; the layout of
@@ -142,19 +129,19 @@ __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles 
 // 0 in slots without a segment), its brick count and the chunk's largest |weight|.
 __global__ __launch_bounds__(256) void tvam_cone_emit_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
                                                              const int32_t* __restrict__ idxmap, TvamSegBuf sb) {
-    const int spp = (int)tp.spp;
     float wmax = 0.0f;
+    const bool f32 = tvam_path_fits32(sb.p1);
     for (int64_t i = sb.p0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < sb.p1;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t slot = i - sb.p0;
         reinterpret_cast<float*>(&sb.r[TVAM_REC_F4 * slot + 2])[2] = 0.0f;
-        const int64_t local = i / spp;
-        const int smp = (int)(i - local * spp);
-        const float p = pat[local];
-        if (p == 0.0f && k.skip_zero) continue;
-        const float em = p * k.wscale * k.inv_vol;
+        TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
+        float em;
+        int64_t act;
+        if (!tvam_path_gate<TVAM_MODE_FWD>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+        tvam_path_pixel(k, f32, ix);
         ConeRay r;
-        if (!cn_ray(k, tp, idxmap, local, smp, r)) continue;
+        if (!cn_ray(k, tp, idxmap, ix, r)) continue;
         SegDda q;
         if (!sc_dda_init(k, r.o2, r.d, r.maxt, q)) continue;
         sb.r[TVAM_REC_F4 * slot] = make_float4(q.t_start, q.tau_end, q.dtm0[0], q.dtm0[1]);
@@ -173,19 +160,18 @@ __global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, Tva
                                                                float* __restrict__ rays) {
     const int spp = (int)tp.spp;
     const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * spp;
+    const bool f32 = tvam_path_fits32(n);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t local = i / spp;
-        const int smp = (int)(i - local * spp);
-        int64_t act = local;
-        if (idxmap) {
-            act = idxmap[local];
-            if (act < 0) continue;
-        }
+        TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
+        float em;
+        int64_t act;
+        if (!tvam_path_gate<TVAM_MODE_ADJ>(k, nullptr, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+        tvam_path_pixel(k, f32, ix);
         ConeRay r;
         r.o2[0] = r.o2[1] = r.o2[2] = 0.0f;
         r.maxt = 0.0f;
-        const bool hit = cn_ray(k, tp, idxmap, local, smp, r);
-        float4* row = reinterpret_cast<float4*>(rays + 16 * (act * spp + smp));
+        const bool hit = cn_ray(k, tp, idxmap, ix, r);
+        float4* row = reinterpret_cast<float4*>(rays + 16 * (act * spp + ix.smp));
         row[0] = make_float4(r.o[0], r.o[1], r.o[2], r.d[0]);
         row[1] = make_float4(r.d[1], r.d[2], hit ? 1.0f : 0.0f, hit ? r.o2[0] : 0.0f);
         row[2] = make_float4(hit ? r.o2[1] : 0.0f, hit ? r.o2[2] : 0.0f, hit ? r.maxt : 0.0f, r.d[0]);
@@ -193,14 +179,12 @@ __global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, Tva
     }
 }
 
-unsigned cn_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 262144); }
-
 }  // namespace
 
 hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                  const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
                                  hipStream_t stream) {
-    const dim3 g(cn_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp)), b(256);
+    const dim3 g(tvam_grid_1d((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp, 262144)), b(256);
     switch (mode) {
         case TVAM_MODE_FWD:
             tvam_kt_begin(stream, TVAM_KT_CONE);
@@ -223,7 +207,7 @@ void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const floa
 
 hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
                                    hipStream_t stream) {
-    const dim3 g(cn_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp)), b(256);
+    const dim3 g(tvam_grid_1d((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp, 262144)), b(256);
     hipLaunchKernelGGL(tvam_cone_export_kernel, g, b, 0, stream, k, t, idxmap, rays);
     return hipGetLastError();
 }

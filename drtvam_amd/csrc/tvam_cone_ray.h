@@ -3,7 +3,7 @@
 // first-hit pass): the sampler draws, get_ray, CircularMotion's to_world and the medium segment
 // behind the index-matched vial (device only).
 #pragma once
-#include "tvam_internal.h"
+#include "tvam_path.h"
 #include "tvam_seg3d.h"
 
 namespace {
@@ -58,29 +58,10 @@ __device__ __forceinline__ bool cn_segment(const TvamConsts& k, ConeRay& r) {
 __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& tp, int al, int colc, int rowc,
                                           uint64_t stream, ConeRay& r) {
     TvamPcg rng;
-    rng.seed(tp.seed, stream);
-    float jx = 0.5f, jy = 0.5f;
-    if (!k.regular) {
-        jx = rng.next_float();
-        jy = rng.next_float();
-    }
-    float c, sn;
-    if (k.sample_time) {  // common.py:101-104: time = (angle + u) / n_patterns
-        float time = (float)(k.a0 + al);
-        time = time + rng.next_float();
-        time = time / (float)k.n_patterns;
-        float alpha = TVAM_TWO_PI * time;
-        if (k.clockwise) alpha = -alpha;
-        c = cosf(alpha);
-        sn = sinf(alpha);
-    } else {
-        const float2 csv = tp.cs[al];
-        c = csv.x;
-        sn = csv.y;
-    }
-    const float u1 = rng.next_float(), u2 = rng.next_float();  // aperture sample (projector.py:160)
+    const TvamPathDraws dr = tvam_path_draws<true, true>(k, tp, al, stream, rng);
+    const float c = dr.c, sn = dr.sn;
     float xc, yc;
-    tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
+    tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, dr.jx, dr.jy, xc, yc);
     if (k.proj_type == TVAM_PROJECTOR_COLLIMATED) {
         tvam_ray_world(k, c, sn, xc, yc, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1]);
         r.d[2] = 0.0f;
@@ -88,7 +69,7 @@ __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& 
         return tvam_segment_im(k, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.o2[0], r.o2[1], r.maxt);
     }
     float ax, ay;
-    cn_disk(u1, u2, ax, ay);
+    cn_disk(dr.u1, dr.u2, ax, ay);
     ax = k.ap_r * ax;
     ay = k.ap_r * ay;
     // camera space: origin (X, Y, 0) on the aperture plane, direction towards the pixel's point of

@@ -21,7 +21,6 @@ __global__ __launch_bounds__(256) void tvam_corner_kernel(TvamConsts k, TvamTile
                                                           const uint32_t* __restrict__ active, int64_t n, float dist,
                                                           float radius, float* __restrict__ keep,
                                                           float4* __restrict__ hits) {
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
     const uint32_t hw = (uint32_t)k.res_x * (uint32_t)k.res_y;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         int al, colc, rowc;
@@ -35,10 +34,7 @@ __global__ __launch_bounds__(256) void tvam_corner_kernel(TvamConsts k, TvamTile
             colc = (int)col - k.crop_off_x;
             stream = (uint64_t)(k.stream_base + i);
         } else {
-            al = (int)(i / per_angle);
-            const int64_t pix = i - (int64_t)al * per_angle;
-            rowc = (int)(pix / k.crop_x);
-            colc = (int)(pix - (int64_t)rowc * k.crop_x);
+            tvam_path_pixel(k, i, tvam_path_fits32(n), al, rowc, colc);
             stream = (uint64_t)(i + k.shard_base);
         }
         TvamFirstHit h;
@@ -47,10 +43,9 @@ __global__ __launch_bounds__(256) void tvam_corner_kernel(TvamConsts k, TvamTile
         if (al >= 0 && al < tp.n_shard) {
             float ox, oy, oz, dx, dy, dz;
             if (PROJ == TVAM_PROJECTOR_COLLIMATED) {
-                const float2 csv = tp.cs[al];
-                float xc, yc;
-                tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, 0.5f, 0.5f, xc, yc);
-                tvam_ray_world(k, csv.x, csv.y, xc, yc, ox, oy, oz, dx, dy);
+                TvamPcg rng;  // (k.regular: nothing is drawn)
+                const TvamPathDraws dr = tvam_path_draws<false, false>(k, tp, al, stream, rng);
+                tvam_path_ray(k, colc, rowc, dr, ox, oy, oz, dx, dy);
                 dz = 0.0f;
             } else {
                 ConeRay r;
@@ -73,10 +68,7 @@ __global__ __launch_bounds__(256) void tvam_corner_kernel(TvamConsts k, TvamTile
 
 hipError_t tvam_launch_corner(const TvamConsts& k, const TvamTiles& t, const uint32_t* active, int64_t n, float dist,
                               float radius, float* keep, float* hits, hipStream_t stream) {
-    int64_t g = (n + 255) / 256;
-    if (g > 65536) g = 65536;
-    if (g < 1) g = 1;
-    const dim3 grid((unsigned)g), block(256);
+    const dim3 grid(tvam_grid_1d(n)), block(256);
     float4* h4 = reinterpret_cast<float4*>(hits);
     switch (k.proj_type) {
         case TVAM_PROJECTOR_COLLIMATED:

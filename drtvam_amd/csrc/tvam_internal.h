@@ -156,6 +156,12 @@ hipError_t tvam_launch_fwd_rays_planar(const TvamConsts& k, const TvamPlanar& pl
                                        const float* pat, unsigned* amax, float* scale, float* dose,
                                        hipStream_t stream);
 
+// Workgroups of 256 threads of a grid-stride launch over n items: ceil(n / 256) in [1, cap].
+inline unsigned tvam_grid_1d(int64_t n, int64_t cap = 65536) {
+    const int64_t g = (n + 255) / 256;
+    return (unsigned)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+
 enum TvamMode { TVAM_MODE_FWD = 0, TVAM_MODE_ADJ = 1, TVAM_MODE_COUNT = 2, TVAM_MODE_EMIT = 3 };
 
 // float4s per brick-bin segment record (48 B; 64-B aligned records measured +0.4 % on config 4:

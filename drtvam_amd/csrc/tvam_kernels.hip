@@ -18,6 +18,7 @@
 //    DDA steps axis a at t_start + dtm0[a] + n*ts[a], so the voxel index and
 //    dtmax at any time follow without marching the skipped part.
 #include "tvam_internal.h"
+#include "tvam_path.h"
 
 #define TVAM_BLOCK 256
 #define TVAM_WAVES (TVAM_BLOCK / 64)
@@ -155,47 +156,18 @@ __device__ __forceinline__ void tvam_append_strays(const TvamTiles& tp, bool s, 
 __global__ __launch_bounds__(256) void tvam_ray_setup_kernel(TvamConsts k, TvamTiles tp, float4* __restrict__ ray_f,
                                                              int2* __restrict__ ray_i, float4* __restrict__ ray_g,
                                                              const int32_t* __restrict__ idxmap) {
-    const int spp = (int)tp.spp;
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
-    const int64_t n_local = (int64_t)tp.n_shard * per_angle;
-    const int64_t n = n_local * spp;
+    const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * tp.spp;
+    const bool f32 = tvam_path_fits32(n);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        // record i = smp * n_local + local (sample-major: the tile kernels' lanes, which enumerate
-        // the sample slowest, read consecutive records of neighbouring pixels)
-        int smp, al, rowc, colc;
-        int64_t local;
-        if (n <= (int64_t)0xffffffff) {  // 32-bit index arithmetic (a 64-bit division is ~3x the code)
-            const uint32_t ii = (uint32_t)i, nl = (uint32_t)n_local, pa = (uint32_t)per_angle, cx = (uint32_t)k.crop_x;
-            const uint32_t s32 = ii / nl, l32 = ii - s32 * nl, a32 = l32 / pa, p32 = l32 - a32 * pa, r32 = p32 / cx;
-            smp = (int)s32;
-            local = (int64_t)l32;
-            al = (int)a32;
-            rowc = (int)r32;
-            colc = (int)(p32 - r32 * cx);
-        } else {
-            smp = (int)(i / n_local);
-            local = i - (int64_t)smp * n_local;
-            al = (int)(local / per_angle);
-            const int64_t pix = local - (int64_t)al * per_angle;
-            rowc = (int)(pix / k.crop_x);
-            colc = (int)(pix - (int64_t)rowc * k.crop_x);
-        }
-        float jx = 0.5f, jy = 0.5f;
-        if (!k.regular) {
-            TvamPcg rng;
-            rng.seed(tp.seed, tvam_stream(k, idxmap, local, (uint32_t)spp, smp));
-            jx = rng.next_float();
-            jy = rng.next_float();
-        }
-        const float2 csv = tp.cs[al];
-        float xc, yc, ox, oy, oz, dx, dy;
-        tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
-        tvam_ray_world(k, csv.x, csv.y, xc, yc, ox, oy, oz, dx, dy);
-        int slice = tvam_slice_of(k, oz);
-        float o2x, o2y, d2x, d2y, maxt, wgt;
+        TvamPathIndex ix = tvam_path_index<true>(k, tp, i, f32);
+        tvam_path_pixel(k, f32, ix);
+        TvamPcg rng;
+        const TvamPathDraws dr = tvam_path_draws<false, false>(k, tp, ix.al, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), rng);
+        TvamPathSeg s;
+        const bool hit = tvam_path_first_segment(k, ix, dr, s);
+        int slice = tvam_slice_of(k, s.oz);
         TvamDda q;
-        if (slice < 0 || !tvam_segment(k, ox, oy, oz, dx, dy, o2x, o2y, d2x, d2y, maxt, wgt) ||
-            !tvam_dda_init(k, o2x, o2y, d2x, d2y, maxt, q)) {
+        if (slice < 0 || !hit || !tvam_dda_init(k, s.o2x, s.o2y, s.d2x, s.d2y, s.maxt, q)) {
             ray_f[i] = make_float4(0.0f, -1.0f, 0.0f, 0.0f);
             ray_i[i] = make_int2(0, -1);
             if (ray_g) ray_g[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -204,8 +176,8 @@ __global__ __launch_bounds__(256) void tvam_ray_setup_kernel(TvamConsts k, TvamT
         ray_f[i] = make_float4(q.t_start, q.tau_end, q.dtm0[0], q.dtm0[1]);
         // an axis that moves but whose first crossing rounded negative never steps (sensor.py:358):
         // the ray leaves its chord, so tvam_frozen_kernel marches it instead of the tile kernels
-        const bool frozen = (fabsf(d2x) > 1e-8f && !(q.dtm0[0] < TVAM_INF)) ||
-                            (fabsf(d2y) > 1e-8f && !(q.dtm0[1] < TVAM_INF));
+        const bool frozen = (fabsf(s.d2x) > 1e-8f && !(q.dtm0[0] < TVAM_INF)) ||
+                            (fabsf(s.d2y) > 1e-8f && !(q.dtm0[1] < TVAM_INF));
         ray_i[i] = make_int2(q.sv[0] | (q.sv[1] << 16), frozen ? -2 - slice : slice);
         if (frozen && tp.frozen) {
             const unsigned long long j = atomicAdd(tp.frozen_n, 1ull);
@@ -214,10 +186,10 @@ __global__ __launch_bounds__(256) void tvam_ray_setup_kernel(TvamConsts k, TvamT
         bool stray = false;
         const int zl = slice - k.z0;
         if (tp.row_main && !frozen) {  // a ray outside its row's main slice (TvamTiles::slice_moff)
-            stray = zl >= 0 && zl < k.nz && zl != tp.row_main[rowc];
+            stray = zl >= 0 && zl < k.nz && zl != tp.row_main[ix.rowc];
         }
         if (ray_g)
-            ray_g[i] = make_float4(q.step[0] > 0 ? q.ts[0] : -q.ts[0], q.step[1] > 0 ? q.ts[1] : -q.ts[1], wgt, 0.0f);
+            ray_g[i] = make_float4(q.step[0] > 0 ? q.ts[0] : -q.ts[0], q.step[1] > 0 ? q.ts[1] : -q.ts[1], s.wgt, 0.0f);
         if (tp.row_main) tvam_append_strays(tp, stray, zl, (uint32_t)i);
     }
 }
@@ -225,10 +197,7 @@ __global__ __launch_bounds__(256) void tvam_ray_setup_kernel(TvamConsts k, TvamT
 hipError_t tvam_launch_ray_setup(const TvamConsts& k, const TvamTiles& t, float4* ray_f, int2* ray_i,
                                  float4* ray_g, const int32_t* idxmap, hipStream_t stream) {
     const int64_t n = (int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp;
-    int64_t g = (n + 255) / 256;
-    if (g > 65536) g = 65536;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(tvam_ray_setup_kernel, dim3((unsigned)g), dim3(256), 0, stream, k, t, ray_f, ray_i, ray_g, idxmap);
+    hipLaunchKernelGGL(tvam_ray_setup_kernel, dim3(tvam_grid_1d(n)), dim3(256), 0, stream, k, t, ray_f, ray_i, ray_g, idxmap);
     return hipGetLastError();
 }
 

@@ -1583,6 +1583,50 @@ static int fwd_chunk(const tvam_plan* p) {
 
 extern "C" int tvam_plan_fwd_chunk(const tvam_plan* p) { return p ? fwd_chunk(p) : 0; }
 
+// The TvamTiles of a call: the plan's tables with the call's spp and seed.
+static TvamTiles call_tiles(const tvam_plan* p, uint32_t spp, uint32_t seed) {
+    TvamTiles t = p->tiles;
+    t.spp = spp;
+    t.seed = seed;
+    return t;
+}
+
+// A sparse active set (active_pixels): the dense (angle,row,col) -> active index map (the adjoint
+// kernels add each ray's gradient straight into grad_active[active index]); with active_data (the
+// forward) also the data scattered into the zeroed dense patterns, *pat.  A dense set binds nothing.
+static int bind_active(tvam_plan* p, const TvamConsts& k, const float* active_data, const uint32_t* active_pixels,
+                       uint64_t n_active, hipStream_t stream, const float** pat, const int32_t** idxmap) {
+    if (!active_pixels) return 0;
+    int rc;
+    hipError_t e = hipSuccess;
+    if ((rc = ensure_dense(p))) return rc;
+    if ((active_data && (e = hipMemsetAsync(p->d_dense, 0, p->dense_n * sizeof(float), stream)) != hipSuccess) ||
+        (e = hipMemsetAsync(p->d_idxmap, 0xff, p->dense_n * sizeof(int32_t), stream)) != hipSuccess)
+        return hip_fail(e, "hipMemsetAsync");
+    if ((e = tvam_launch_scatter(k, active_data, active_pixels, n_active, p->d_dense, p->d_idxmap, stream)) !=
+        hipSuccess)
+        return hip_fail(e, "scatter launch");
+    if (active_data) *pat = p->d_dense;
+    *idxmap = p->d_idxmap;
+    return 0;
+}
+
+// Scattered segments of a call (after each path's first medium segment): through the brick bins,
+// else (by flag, or a grid beyond the packed records' range) the per-path atomics / gathers.
+static int scattered_segments(int mode, tvam_plan* p, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                              const int32_t* idxmap, const float* gin, float* out, hipStream_t stream) {
+    const bool fwd = mode == TVAM_MODE_FWD;
+    hipError_t e = hipErrorNotSupported;
+    if (fwd) p->bins.acc_float = env_int("TVAM_BIN_FLOAT", 0);
+    if (p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC)
+        for (auto& v : p->bins.st) v = 0;  // nothing binned
+    else
+        e = tvam_scatter_binned(mode, k, t, pat, idxmap, gin, out, p->bins, stream);
+    if (e == hipErrorNotSupported) e = tvam_launch_scatter_paths(mode, k, t, pat, idxmap, gin, out, nullptr, stream);
+    if (e == hipErrorIllegalState) return bin_mismatch_fail(p);
+    return e == hipSuccess ? 0 : hip_fail(e, fwd ? "scatter forward launch" : "scatter adjoint launch");
+}
+
 static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* active_pixels, uint64_t n_active,
                         uint32_t spp, uint32_t seed, float* dose, void* stream_, int zb, int ze);
 
@@ -1623,21 +1667,9 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
     }
     const float* pat = active_data;
     const int32_t* idxmap = nullptr;
-    if (active_pixels) {
-        if ((rc = ensure_dense(p))) return rc;
-        if ((e = hipMemsetAsync(p->d_dense, 0, p->dense_n * sizeof(float), stream)) != hipSuccess ||
-            (e = hipMemsetAsync(p->d_idxmap, 0xff, p->dense_n * sizeof(int32_t), stream)) != hipSuccess)
-            return hip_fail(e, "hipMemsetAsync");
-        if ((e = tvam_launch_scatter(kc, active_data, active_pixels, n_active, p->d_dense, p->d_idxmap, stream)) !=
-            hipSuccess)
-            return hip_fail(e, "scatter launch");
-        pat = p->d_dense;
-        idxmap = p->d_idxmap;
-    }
+    if ((rc = bind_active(p, kc, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
     if (p->general) {
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
+        TvamTiles t = call_tiles(p, spp, seed);
         if (p->cone) {
             // the brick-binned forward or the per-ray atomics: by flag, else the plan's default
             const int fl = p->desc.flags;
@@ -1658,9 +1690,7 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
         return e == hipSuccess ? 0 : hip_fail(e, "path forward launch");
     }
     if (p->surface) {
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
+        TvamTiles t = call_tiles(p, spp, seed);
         e = tvam_launch_surface_paths(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, p->vols, dose, nullptr, stream);
         if (e == hipSuccess) e = tvam_launch_scale_volumes((int64_t)V, p->vols, dose, stream);
         return e == hipSuccess ? 0 : hip_fail(e, "surface-aware forward launch");
@@ -1681,9 +1711,7 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
         e = tvam_launch_fwd_rays_planar(kc, p->pl, p->tiles, p->planar_rz, pat, p->d_amax, p->d_fscale, dose, stream);
         if (e != hipSuccess) return hip_fail(e, "planar ray forward launch");
     } else {
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
+        TvamTiles t = call_tiles(p, spp, seed);
         if (ranged) {
             t.kz0 = zb;
             t.kz1 = ze;
@@ -1702,19 +1730,7 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
         if (e != hipSuccess) return hip_fail(e, "forward launch");
     }
     if (p->desc.albedo != 0.0f) {  // scattered segments (after each path's first medium segment)
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
-        e = hipErrorNotSupported;
-        p->bins.acc_float = env_int("TVAM_BIN_FLOAT", 0);
-        if (p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC)
-            for (auto& v : p->bins.st) v = 0;  // nothing binned
-        else
-            e = tvam_scatter_binned(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, p->bins, stream);
-        if (e == hipErrorNotSupported)
-            e = tvam_launch_scatter_paths(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, nullptr, stream);
-        if (e == hipErrorIllegalState) return bin_mismatch_fail(p);
-        if (e != hipSuccess) return hip_fail(e, "scatter forward launch");
+        return scattered_segments(TVAM_MODE_FWD, p, kc, call_tiles(p, spp, seed), pat, idxmap, nullptr, dose, stream);
     }
     return 0;
 }
@@ -1790,25 +1806,13 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     hipError_t e;
     if (n_active == 0) return 0;
     const int32_t* idxmap = nullptr;
-    if (active_pixels) {
-        // dense (angle,row,col) -> active index map; the kernel adds each
-        // ray's gradient straight into grad_active[active index]
-        if ((rc = ensure_dense(p))) return rc;
-        if ((e = hipMemsetAsync(p->d_idxmap, 0xff, p->dense_n * sizeof(int32_t), stream)) != hipSuccess)
-            return hip_fail(e, "hipMemsetAsync");
-        if ((e = tvam_launch_scatter(k, nullptr, active_pixels, n_active, p->d_dense, p->d_idxmap, stream)) !=
-            hipSuccess)
-            return hip_fail(e, "scatter launch");
-        idxmap = p->d_idxmap;
-    }
+    if ((rc = bind_active(p, k, nullptr, active_pixels, n_active, stream, nullptr, &idxmap))) return rc;
     if ((rc = ensure_adj_lists(p))) return rc;
     if ((e = hipMemsetAsync(grad_active, 0, n_active * sizeof(float), stream)) != hipSuccess)
         return hip_fail(e, "hipMemsetAsync");
     if (p->general) {
         if (p->empty) return 0;
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
+        TvamTiles t = call_tiles(p, spp, seed);
         e = p->cone ? tvam_launch_cone_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
                     : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
         return e == hipSuccess ? 0 : hip_fail(e, "path adjoint launch");
@@ -1816,9 +1820,7 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     if (p->surface) {
         if (!p->vols) return fail(TVAM_ERR_INVALID, "surface-aware film: call tvam_plan_set_volumes first");
         if (p->empty) return 0;
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
+        TvamTiles t = call_tiles(p, spp, seed);
         e = tvam_launch_surface_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, p->vols, grad_active, nullptr,
                                       stream);
         return e == hipSuccess ? 0 : hip_fail(e, "surface-aware adjoint launch");
@@ -1827,9 +1829,7 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
         e = tvam_launch_adj_planar(k, p->pl, p->tiles, p->planar_az, idxmap, grad_dose, grad_active, stream);
         if (e != hipSuccess) return hip_fail(e, "planar adjoint launch");
     } else if (!p->empty) {
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
+        TvamTiles t = call_tiles(p, spp, seed);
         if ((rc = ensure_rays(p, k, t, idxmap, stream, active_pixels, n_active))) return rc;
         e = tvam_launch_tiles(TVAM_MODE_ADJ, k, t, p->lds_bytes, nullptr, idxmap, grad_dose, grad_active, nullptr,
                               stream);
@@ -1838,18 +1838,8 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
         if (e != hipSuccess) return hip_fail(e, "adjoint launch");
     }
     if (p->desc.albedo != 0.0f && !p->empty) {
-        TvamTiles t = p->tiles;
-        t.spp = spp;
-        t.seed = seed;
-        e = hipErrorNotSupported;
-        if (p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC)
-            for (auto& v : p->bins.st) v = 0;  // nothing binned
-        else
-            e = tvam_scatter_binned(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, p->bins, stream);
-        if (e == hipErrorNotSupported)
-            e = tvam_launch_scatter_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
-        if (e == hipErrorIllegalState) return bin_mismatch_fail(p);
-        if (e != hipSuccess) return hip_fail(e, "scatter adjoint launch");
+        return scattered_segments(TVAM_MODE_ADJ, p, k, call_tiles(p, spp, seed), nullptr, idxmap, grad_dose, grad_active,
+                                  stream);
     }
     return 0;
 }
@@ -1868,17 +1858,8 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
     if (n_active == 0) return 0;
     hipError_t e;
     const int32_t* idxmap = nullptr;
-    if (active_pixels) {
-        if ((rc = ensure_dense(p))) return rc;
-        if ((e = hipMemsetAsync(p->d_idxmap, 0xff, p->dense_n * sizeof(int32_t), stream)) != hipSuccess)
-            return hip_fail(e, "hipMemsetAsync");
-        if ((e = tvam_launch_scatter(k, nullptr, active_pixels, n_active, p->d_dense, p->d_idxmap, stream)) != hipSuccess)
-            return hip_fail(e, "scatter launch");
-        idxmap = p->d_idxmap;
-    }
-    TvamTiles t = p->tiles;
-    t.spp = spp;
-    t.seed = seed;
+    if ((rc = bind_active(p, k, nullptr, active_pixels, n_active, stream, nullptr, &idxmap))) return rc;
+    TvamTiles t = call_tiles(p, spp, seed);
     e = tvam_launch_cone_export(k, t, idxmap, rays, stream);
     return e == hipSuccess ? 0 : hip_fail(e, "ray export launch");
 }
@@ -1894,9 +1875,7 @@ extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint
     if (p->empty) return 0;
     hipError_t e = hipMemset(p->d_counter, 0, sizeof(unsigned long long));
     if (e != hipSuccess) return hip_fail(e, "hipMemset");
-    TvamTiles t = p->tiles;
-    t.spp = spp;
-    t.seed = seed;
+    TvamTiles t = call_tiles(p, spp, seed);
     if (p->general) {
         e = p->cone ? tvam_launch_cone_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->d_counter, nullptr)
                     : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->d_counter, nullptr);
@@ -1947,9 +1926,7 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
     // ray weight inv_pdf / n / spp * print_time (projector.py:164-165, common.py:111)
     const float area = d.pixel_size_x * d.pixel_size_y * (float)n;
     const float wray = area / (float)(n * (uint64_t)spp) * d.print_time;
-    TvamTiles t = p->tiles;
-    t.spp = spp;
-    t.seed = seed;
+    TvamTiles t = call_tiles(p, spp, seed);
     e = tvam_launch_radon(k, t, dt, n_target_tris, max_depth, wray, radon, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     (void)hipFree(dt);

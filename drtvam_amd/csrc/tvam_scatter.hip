@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "tvam_path.h"
 #include "tvam_seg3d.h"
 
 namespace {
@@ -50,55 +51,7 @@ __device__ __forceinline__ float sc_container_hit(const TvamConsts& k, float ox,
     return t;
 }
 
-// Mitsuba coordinate_system() (Duff et al. 2017) and the phase functions'
-// sample(): isotropic (square_to_uniform_sphere, world space), rayleigh (cbrt
-// inversion of the (3/8)(1 + mu^2) CDF), hg (-cos_theta in the frame of wi).
-__device__ __forceinline__ void sc_phase(const TvamConsts& k, float dx, float dy, float dz, float u1, float u2,
-                                         float& wx, float& wy, float& wz) {
-    float lx, ly, lz;
-    if (k.phase_type == TVAM_PHASE_ISOTROPIC) {  // square_to_uniform_sphere(u): z = 1 - 2 u.y, phi = 2 pi u.x
-        const float z = 1.0f - 2.0f * u2;
-        const float r = sqrtf(fmaxf(1.0f - z * z, 0.0f));
-        const float sp = sinf(TVAM_TWO_PI * u1), cp = cosf(TVAM_TWO_PI * u1);
-        wx = r * cp;
-        wy = r * sp;
-        wz = z;
-        return;
-    }
-    if (k.phase_type == TVAM_PHASE_RAYLEIGH) {
-        const float z = 2.0f * (2.0f * u1 - 1.0f);
-        const float tmp = sqrtf(z * z + 1.0f);
-        const float ct = cbrtf(z + tmp) + cbrtf(z - tmp);
-        const float st = sqrtf(fmaxf(1.0f - ct * ct, 0.0f));
-        const float sp = sinf(TVAM_TWO_PI * u2), cp = cosf(TVAM_TWO_PI * u2);
-        lx = st * cp;
-        ly = st * sp;
-        lz = ct;
-    } else {
-        const float g = k.phase_g;
-        float ct;
-        if (fabsf(g) < 5.9604644775390625e-08f) {
-            ct = 1.0f - 2.0f * u1;
-        } else {
-            const float sq = (1.0f - g * g) / (1.0f - g + 2.0f * g * u1);
-            ct = (1.0f + g * g - sq * sq) / (2.0f * g);
-        }
-        const float st = sqrtf(fmaxf(1.0f - ct * ct, 0.0f));
-        const float sp = sinf(TVAM_TWO_PI * u2), cp = cosf(TVAM_TWO_PI * u2);
-        lx = st * cp;
-        ly = st * sp;
-        lz = -ct;
-    }
-    const float nx = -dx, ny = -dy, nz = -dz;  // Frame3f(wi = -d)
-    const float sg = copysignf(1.0f, nz);
-    const float a = -1.0f / (sg + nz);
-    const float b = nx * ny * a;
-    const float sx = sg * (nx * nx * a) + 1.0f, sy = sg * b, sz = -sg * nx;
-    const float tx = b, ty = fmaf(ny, ny * a, sg), tz = -ny;
-    wx = sx * lx + tx * ly + nx * lz;
-    wy = sy * lx + ty * ly + ny * lz;
-    wz = sz * lx + tz * ly + nz * lz;
-}
+// sc_phase, sc_roulette, sc_medium_event, sc_ratio_track, sc_point_voxel: tvam_path.h
 
 // ---------------------------------------------------------------------------
 // Brick-binned forward of the scattered segments.  A segment's DDA state after
@@ -186,12 +139,9 @@ __global__ __launch_bounds__(256) void tvam_scatter_kernel(TvamConsts k, TvamTil
                                                            const int32_t* __restrict__ idxmap,
                                                            const float* __restrict__ gin, float* __restrict__ out,
                                                            unsigned long long* __restrict__ counter, TvamSegBuf sb) {
-    const int spp = (int)tp.spp;
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
-    const int64_t n = MODE == TVAM_MODE_EMIT ? sb.p1 : (int64_t)tp.n_shard * per_angle * spp;
+    const int64_t n = MODE == TVAM_MODE_EMIT ? sb.p1 : (int64_t)tp.n_shard * k.crop_y * k.crop_x * tp.spp;
     const int64_t i0 = MODE == TVAM_MODE_EMIT ? sb.p0 : 0;
-    const float st = k.sig_t, ss = k.sig_s;
-    const int nsurf = k.vial_type == 0 ? 1 : 2;  // glass vials: two surfaces before the medium
+    const int nsurf = sc_nsurf(k);  // glass vials: two surfaces before the medium
     uint64_t nvis = 0;
     float wmax = 0.0f;  // EMIT (forward): largest |record weight| of this thread's paths
     // EMIT with sb.hist: this workgroup's entries per brick (LDS), written to hist[brick][block]:
@@ -203,75 +153,42 @@ __global__ __launch_bounds__(256) void tvam_scatter_kernel(TvamConsts k, TvamTil
         for (int b = threadIdx.x; b < sb.nbricks; b += blockDim.x) s_hist[b] = 0u;
         __syncthreads();
     }
+    const bool f32 = tvam_path_fits32(n);
     for (int64_t i = i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         if (MODE == TVAM_MODE_EMIT && !sb.adj)  // slots without a segment: attenuation 0 (the cache's rescale)
             for (int q = 0; q < sb.slots; ++q) reinterpret_cast<float*>(&sb.r[TVAM_REC_F4 * ((i - sb.p0) * sb.slots + q) + 2])[2] = 0.0f;
-        int64_t local;
-        int smp, al, rowc, colc;
-        if (n <= (int64_t)0xffffffff) {  // 32-bit index arithmetic (a 64-bit division is ~3x the code)
-            const uint32_t ii = (uint32_t)i, sp = (uint32_t)spp, pa = (uint32_t)per_angle, cx = (uint32_t)k.crop_x;
-            const uint32_t l32 = ii / sp, a32 = l32 / pa, p32 = l32 - a32 * pa, r32 = p32 / cx;
-            local = (int64_t)l32;
-            smp = (int)(ii - l32 * sp);
-            al = (int)a32;
-            rowc = (int)r32;
-            colc = (int)(p32 - r32 * cx);
-        } else {
-            local = i / spp;
-            smp = (int)(i - local * spp);
-            al = (int)(local / per_angle);
-            const int64_t pix = local - (int64_t)al * per_angle;
-            rowc = (int)(pix / k.crop_x);
-            colc = (int)(pix - (int64_t)rowc * k.crop_x);
+        TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
+        float em;
+        int64_t act;
+        if (MODE == TVAM_MODE_EMIT) {  // forward records: the forward's gate; adjoint records: weight
+            if (!sb.adj) {             // att * wscale (grad * inv_vol gathered)
+                if (!tvam_path_gate<TVAM_MODE_FWD>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+            } else {
+                if (!tvam_path_gate<TVAM_MODE_ADJ>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+                em = k.wscale;
+            }
+        } else if (!tvam_path_gate<MODE>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) {
+            continue;
         }
-        float em = 1.0f;
-        int64_t act = local;
-        if (MODE == TVAM_MODE_FWD || (MODE == TVAM_MODE_EMIT && !sb.adj)) {
-            const float p = pat[local];
-            if (p == 0.0f && k.skip_zero) continue;
-            em = p * k.wscale * k.inv_vol;
-        } else if (MODE == TVAM_MODE_EMIT) {  // adjoint records: weight att * wscale (grad * inv_vol gathered)
-            em = k.wscale;
-            if (idxmap && idxmap[local] < 0) continue;
-        } else if (idxmap) {
-            act = idxmap[local];
-            if (act < 0) continue;
-        }
+        tvam_path_pixel(k, f32, ix);
         TvamPcg rng;
-        rng.seed(tp.seed, tvam_stream(k, idxmap, local, (uint32_t)spp, smp));
-        float jx = 0.5f, jy = 0.5f;
-        if (!k.regular) {
-            jx = rng.next_float();
-            jy = rng.next_float();
-        }
-        (void)rng.next_float();  // aperture sample (projector.py:160)
-        (void)rng.next_float();
-        const float2 csv = tp.cs[al];
-        float xc, yc, ox, oy, oz, dx, dy;
-        tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
-        tvam_ray_world(k, csv.x, csv.y, xc, yc, ox, oy, oz, dx, dy);
-        float o2x, o2y, d2x, d2y, maxt, wgt;
-        if (!tvam_segment(k, ox, oy, oz, dx, dy, o2x, o2y, d2x, d2y, maxt, wgt)) continue;
-        for (int q = 0; q < 5 * nsurf; ++q) (void)rng.next_float();  // surface iterations: RR, medium, BSDF
-        float px = o2x, py = o2y, pz = oz, vx = d2x, vy = d2y, vz = 0.0f;
-        float att = wgt;
+        const TvamPathDraws dr = tvam_path_draws<true, false>(k, tp, ix.al, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), rng);
+        TvamPathSeg s;
+        if (!tvam_path_first_segment(k, ix, dr, s)) continue;
+        sc_skip_surface_draws(rng, nsurf, true);
+        float px = s.o2x, py = s.o2y, pz = s.oz, vx = s.d2x, vy = s.d2y, vz = 0.0f;
+        float att = s.wgt;
         int depth = nsurf;
         float acc = 0.0f;
         for (int seg = 0;; ++seg) {
-            const float q = fminf(0.99f, att);
-            const float u_rr = rng.next_float();
-            if (depth > k.rr_depth) {  // Russian roulette (volume.py:182-185)
-                if (!(u_rr < q)) break;
-                att = att * (1.0f / q);
-            }
-            if (!(att != 0.0f)) break;
-            float tsi = maxt;
+            if (!sc_roulette(k, rng, depth, att)) break;
+            float tsi = s.maxt;
             if (seg > 0) {
                 tsi = sc_container_hit(k, px, py, pz, vx, vy, vz);
                 if (!(tsi < TVAM_INF)) break;  // escapes through an open end: no surface, no deposit
             }
             const float u_m = rng.next_float();
-            const float tmi = -logf(1.0f - u_m) / st;
+            const float tmi = -logf(1.0f - u_m) / k.sig_t;
             if (seg > 0 && MODE == TVAM_MODE_EMIT) {
                 const float o[3] = {px, py, pz}, dv[3] = {vx, vy, vz};
                 SegDda q;
@@ -295,31 +212,11 @@ __global__ __launch_bounds__(256) void tvam_scatter_kernel(TvamConsts k, TvamTil
                 if (MODE == TVAM_MODE_ADJ) acc = fmaf(att, r, acc);
             }
             if (tsi < tmi) break;  // leaves the medium for good (transmission only, convex tubes)
-            const float tr = expf(-tmi * st);
-            const float pdf = tr * st;
-            const float inv = pdf > 0.0f ? 1.0f / pdf : 0.0f;
-            float w = tr * inv;
-            w = w * ss;
-            (void)rng.next_float();  // phase next_1d
-            const float u1 = rng.next_float(), u2 = rng.next_float();
-            float wx, wy, wz;
-            sc_phase(k, vx, vy, vz, u1, u2, wx, wy, wz);
-            px = fmaf(vx, tmi, px);
-            py = fmaf(vy, tmi, py);
-            pz = fmaf(vz, tmi, pz);
-            vx = wx;
-            vy = wy;
-            vz = wz;
-            att = att * w;
-            ++depth;
-            if (depth >= k.max_depth) break;
+            if (!sc_medium_event(k, rng, tmi, px, py, pz, vx, vy, vz, att, depth)) break;
         }
         if (MODE == TVAM_MODE_ADJ && acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
     }
-    if (MODE == TVAM_MODE_COUNT) {
-        for (int off = 32; off > 0; off >>= 1) nvis += __shfl_down(nvis, off, 64);
-        if ((threadIdx.x & 63) == 0 && nvis) atomicAdd(counter, (unsigned long long)nvis);
-    }
+    if (MODE == TVAM_MODE_COUNT) tvam_count_reduce(nvis, counter);
     if (MODE == TVAM_MODE_EMIT && !sb.adj) sc_block_max(wmax, sb.wmax);
     if (hist) {
         __syncthreads();
@@ -346,53 +243,32 @@ __global__ __launch_bounds__(256) void tvam_frozen_kernel(TvamConsts k, TvamTile
                                                           const int32_t* __restrict__ idxmap,
                                                           const float* __restrict__ gin, float* __restrict__ out,
                                                           unsigned long long* __restrict__ counter) {
-    const int spp = (int)tp.spp;
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
     // the appended list when it held every frozen ray, else a scan of all ray records
     const unsigned long long nf = *tp.frozen_n;
     const bool list = (int64_t)nf <= tp.frozen_cap;
-    const int64_t n = list ? (int64_t)nf : (int64_t)tp.n_shard * per_angle * spp;
+    const int64_t n = list ? (int64_t)nf : (int64_t)tp.n_shard * k.crop_y * k.crop_x * tp.spp;
     uint64_t nvis = 0;
+    const bool f32 = false;  // (the 64-bit decode alone: the second one costs the count kernel its 5th wave/SIMD)
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = list ? tp.frozen[j] : j;
         const int iy = tp.ray_i[i].y;
         if (iy > -2) continue;
         if (MODE == TVAM_MODE_FWD && tp.kz1 > tp.kz0 && !(-2 - iy >= k.z0 + tp.kz0 && -2 - iy < k.z0 + tp.kz1))
             continue;  // a slice-range forward: another range's frozen ray (it stays in its slice)
-        const int64_t n_local = (int64_t)tp.n_shard * per_angle;  // sample-major ray records
-        const int smp = (int)(i / n_local);
-        const int64_t local = i - (int64_t)smp * n_local;
-        float em = 1.0f;
-        int64_t act = local;
-        if (MODE == TVAM_MODE_FWD) {
-            const float p = pat[local];
-            if (p == 0.0f && k.skip_zero) continue;
-            em = p * k.wscale * k.inv_vol;
-        } else if (MODE == TVAM_MODE_ADJ && idxmap) {
-            act = idxmap[local];
-            if (act < 0) continue;
-        }
-        const int al = (int)(local / per_angle);
-        const int64_t pix = local - (int64_t)al * per_angle;
-        const int rowc = (int)(pix / k.crop_x), colc = (int)(pix - (int64_t)rowc * k.crop_x);
-        float jx = 0.5f, jy = 0.5f;
-        if (!k.regular) {
-            TvamPcg rng;
-            rng.seed(tp.seed, tvam_stream(k, idxmap, local, (uint32_t)spp, smp));
-            jx = rng.next_float();
-            jy = rng.next_float();
-        }
-        const float2 csv = tp.cs[al];
-        float xc, yc, ox, oy, oz, dx, dy;
-        tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
-        tvam_ray_world(k, csv.x, csv.y, xc, yc, ox, oy, oz, dx, dy);
-        float o2x, o2y, d2x, d2y, maxt, wgt;
-        if (!tvam_segment(k, ox, oy, oz, dx, dy, o2x, o2y, d2x, d2y, maxt, wgt)) continue;
-        const float o[3] = {o2x, o2y, oz}, dv[3] = {d2x, d2y, 0.0f};
+        TvamPathIndex ix = tvam_path_index<true>(k, tp, i, f32);  // sample-major ray records
+        float em;
+        int64_t act;
+        if (!tvam_path_gate<MODE>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+        tvam_path_pixel(k, f32, ix);
+        TvamPcg rng;
+        const TvamPathDraws dr = tvam_path_draws<false, false>(k, tp, ix.al, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), rng);
+        TvamPathSeg s;
+        if (!tvam_path_first_segment(k, ix, dr, s)) continue;
+        const float o[3] = {s.o2x, s.o2y, s.oz}, dv[3] = {s.d2x, s.d2y, 0.0f};
         SegDda q;
-        if (!sc_dda_init(k, o, dv, maxt, q)) continue;
+        if (!sc_dda_init(k, o, dv, s.maxt, q)) continue;
         const int64_t sy = k.res[0], sz = (int64_t)k.res[0] * k.res[1];
-        const float emw = em * wgt;
+        const float emw = em * s.wgt;
         float acc = 0.0f;
         sc_seg_march(k, q, [&](int x, int y, int z, float c) {
             if (z < k.z0 || z >= k.z0 + k.nz) return;  // outside this plan's film slab
@@ -401,12 +277,9 @@ __global__ __launch_bounds__(256) void tvam_frozen_kernel(TvamConsts k, TvamTile
             else if (MODE == TVAM_MODE_ADJ) acc = fmaf(c, gin[idx] * k.inv_vol, acc);
             ++nvis;
         });
-        if (MODE == TVAM_MODE_ADJ && acc != 0.0f) atomicAdd(&out[act], acc * wgt * k.wscale);
+        if (MODE == TVAM_MODE_ADJ && acc != 0.0f) atomicAdd(&out[act], acc * s.wgt * k.wscale);
     }
-    if (MODE == TVAM_MODE_COUNT) {
-        for (int off = 32; off > 0; off >>= 1) nvis += __shfl_down(nvis, off, 64);
-        if ((threadIdx.x & 63) == 0 && nvis) atomicAdd(counter, (unsigned long long)nvis);
-    }
+    if (MODE == TVAM_MODE_COUNT) tvam_count_reduce(nvis, counter);
 }
 
 // ---------------------------------------------------------------------------
@@ -462,11 +335,9 @@ template <int MODE>
 __device__ __forceinline__ float sf_point(const TvamConsts& k, float px, float py, float pz, float w, int ch,
                                           float* __restrict__ film, const float* __restrict__ gin,
                                           const float* __restrict__ vols, uint64_t& nvis) {
-    const int vx = (int)floorf((px - k.bmin[0]) / k.h[0]);
-    const int vy = (int)floorf((py - k.bmin[1]) / k.h[1]);
-    const int vz = (int)floorf((pz - k.bmin[2]) / k.h[2]);
-    if (vx < 0 || vy < 0 || vz < 0 || vx >= k.res[0] || vy >= k.res[1] || vz >= k.res[2]) return 0.0f;
-    const int64_t idx = 2 * (vx + (int64_t)vy * k.res[0] + (int64_t)vz * k.res[0] * k.res[1]) + ch;
+    const int64_t vox = sc_point_voxel(k, px, py, pz);
+    if (vox < 0) return 0.0f;
+    const int64_t idx = 2 * vox + ch;
     ++nvis;
     if (MODE == TVAM_MODE_FWD) atomicAdd(&film[idx], w);
     else if (MODE == TVAM_MODE_ADJ) {
@@ -489,63 +360,30 @@ __global__ __launch_bounds__(256) void tvam_surface_kernel(TvamConsts k, TvamTil
                                                            const float* __restrict__ gin,
                                                            const float* __restrict__ vols, float* __restrict__ out,
                                                            unsigned long long* __restrict__ counter) {
-    const int spp = (int)tp.spp;
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
-    const int64_t n = (int64_t)tp.n_shard * per_angle * spp;
-    const float st = k.sig_t, ss = k.sig_s, mj = k.majorant;
-    const bool has_sc = ss != 0.0f;
+    const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * tp.spp;
+    const float st = k.sig_t;
+    const bool has_sc = k.sig_s != 0.0f;
+    const int nsurf = sc_nsurf(k);
     uint64_t nvis = 0;
+    const bool f32 = tvam_path_fits32(n);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t local = i / spp;
-        const int smp = (int)(i - local * spp);
-        float em = 1.0f;
-        int64_t act = local;
-        if (MODE == TVAM_MODE_FWD) {
-            const float p = pat[local];
-            if (p == 0.0f && k.skip_zero) continue;
-            em = p * k.wscale;
-        } else if (idxmap) {
-            act = idxmap[local];
-            if (act < 0) continue;
-        }
-        const int al = (int)(local / per_angle);
-        const int64_t pix = local - (int64_t)al * per_angle;
-        const int rowc = (int)(pix / k.crop_x), colc = (int)(pix - (int64_t)rowc * k.crop_x);
-        float jx = 0.5f, jy = 0.5f;
+        TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
+        float em;
+        int64_t act;
+        // (the unscaled film: tvam_launch_scale_volumes divides by the channels' volumes)
+        if (!tvam_path_gate<MODE>(k, pat, idxmap, ix.local, k.wscale, 1.0f, em, act)) continue;
+        tvam_path_pixel(k, f32, ix);
         TvamPcg rng;
-        if (!k.regular || RNG) {
-            rng.seed(tp.seed, tvam_stream(k, idxmap, local, (uint32_t)spp, smp));
-            if (!k.regular) {
-                jx = rng.next_float();
-                jy = rng.next_float();
-            }
-        }
-        const float2 csv = tp.cs[al];
-        float xc, yc, ox, oy, oz, dx, dy;
-        tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
-        tvam_ray_world(k, csv.x, csv.y, xc, yc, ox, oy, oz, dx, dy);
-        float o2x, o2y, d2x, d2y, maxt, wgt;
-        if (!tvam_segment(k, ox, oy, oz, dx, dy, o2x, o2y, d2x, d2y, maxt, wgt)) continue;
-        const int nsurf = k.vial_type == 0 ? 1 : 2;
-        if (RNG) {
-            (void)rng.next_float();  // aperture sample (projector.py:160)
-            (void)rng.next_float();
-            for (int q = 0; q < (has_sc ? 5 : 4) * nsurf; ++q) (void)rng.next_float();  // RR, (medium), BSDF
-        }
-        float px = o2x, py = o2y, pz = oz;
-        float vx = d2x, vy = d2y, vz = 0.0f;
-        float att = wgt, tcont = maxt, acc = 0.0f;
+        const TvamPathDraws dr = tvam_path_draws<RNG, false>(k, tp, ix.al, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), rng);
+        TvamPathSeg s;
+        if (!tvam_path_first_segment(k, ix, dr, s)) continue;
+        if (RNG) sc_skip_surface_draws(rng, nsurf, has_sc);
+        float px = s.o2x, py = s.o2y, pz = s.oz;
+        float vx = s.d2x, vy = s.d2y, vz = 0.0f;
+        float att = s.wgt, tcont = s.maxt, acc = 0.0f;
         int inside = 0, depth = nsurf;
         for (int it = 0; it < 4096; ++it) {
-            if (RNG) {
-                const float q = fminf(0.99f, att);
-                const float u_rr = rng.next_float();
-                if (depth > k.rr_depth) {  // Russian roulette (volume.py:182-185)
-                    if (!(u_rr < q)) break;
-                    att = att * (1.0f / q);
-                }
-                if (!(att != 0.0f)) break;
-            }
+            if (RNG && !sc_roulette(k, rng, depth, att)) break;
             int tri;
             const float tt = sf_target_hit(k, px, py, pz, vx, vy, vz, tri);
             const bool hit = tt < tcont;
@@ -558,41 +396,18 @@ __global__ __launch_bounds__(256) void tvam_surface_kernel(TvamConsts k, TvamTil
                 const float r = sf_dda<MODE>(k, px, py, pz, vx, vy, vz, tsi, em * att, ch, out, gin, vols, nvis);
                 if (MODE == TVAM_MODE_ADJ) acc = fmaf(att, r, acc);
             } else if (RNG && k.sensor_type == TVAM_SENSOR_RATIO) {
-                const float ratio = st / mj, keep = 1.0f - ratio;
-                float t = 0.0f, pk = 1.0f;
-                for (int s2 = 0; s2 < (1 << 20); ++s2) {
-                    t = t + (-logf(1.0f - rng.next_float()) / mj);
-                    if (!(t < tsi)) break;
-                    const float w = att * pk * ratio;
+                sc_ratio_track(k, rng, tsi, att, [&](float t, float w) {
                     const float r = sf_point<MODE>(k, fmaf(vx, t, px), fmaf(vy, t, py), fmaf(vz, t, pz), em * w, ch, out,
                                                    gin, vols, nvis);
                     if (MODE == TVAM_MODE_ADJ) acc += r;
-                    pk = pk * keep;
-                }
+                });
             } else if (RNG && !reached) {  // delta: the medium interaction ray(mei.t)
                 const float r = sf_point<MODE>(k, fmaf(vx, tmi, px), fmaf(vy, tmi, py), fmaf(vz, tmi, pz), em * att, ch,
                                                out, gin, vols, nvis);
                 if (MODE == TVAM_MODE_ADJ) acc += r;
             }
             if (RNG && !reached) {  // a medium event before the surface: phase sampling
-                const float tr = expf(-tmi * st);
-                const float pdf = tr * st;
-                const float inv = pdf > 0.0f ? 1.0f / pdf : 0.0f;
-                float w = tr * inv;
-                w = w * ss;
-                (void)rng.next_float();  // phase next_1d
-                const float u1 = rng.next_float(), u2 = rng.next_float();
-                float wx, wy, wz;
-                sc_phase(k, vx, vy, vz, u1, u2, wx, wy, wz);
-                px = fmaf(vx, tmi, px);
-                py = fmaf(vy, tmi, py);
-                pz = fmaf(vz, tmi, pz);
-                vx = wx;
-                vy = wy;
-                vz = wz;
-                att = att * w;
-                ++depth;
-                if (depth >= k.max_depth) break;
+                if (!sc_medium_event(k, rng, tmi, px, py, pz, vx, vy, vz, att, depth)) break;
                 tcont = sc_container_hit(k, px, py, pz, vx, vy, vz);
                 if (!(tcont < TVAM_INF)) break;  // escapes through an open end
                 continue;
@@ -630,10 +445,7 @@ __global__ __launch_bounds__(256) void tvam_surface_kernel(TvamConsts k, TvamTil
         }
         if (MODE == TVAM_MODE_ADJ && acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
     }
-    if (MODE == TVAM_MODE_COUNT) {
-        for (int off = 32; off > 0; off >>= 1) nvis += __shfl_down(nvis, off, 64);
-        if ((threadIdx.x & 63) == 0 && nvis) atomicAdd(counter, (unsigned long long)nvis);
-    }
+    if (MODE == TVAM_MODE_COUNT) tvam_count_reduce(nvis, counter);
 }
 
 // ---------------------------------------------------------------------------
@@ -653,11 +465,8 @@ __global__ __launch_bounds__(256) void tvam_surface_kernel(TvamConsts k, TvamTil
 template <int MODE>
 __device__ __forceinline__ float gp_point(const TvamConsts& k, float px, float py, float pz, float w,
                                           float* __restrict__ out, const float* __restrict__ gin, uint64_t& nvis) {
-    const int vx = (int)floorf((px - k.bmin[0]) / k.h[0]);
-    const int vy = (int)floorf((py - k.bmin[1]) / k.h[1]);
-    const int vz = (int)floorf((pz - k.bmin[2]) / k.h[2]);
-    if (vx < 0 || vy < 0 || vz < 0 || vx >= k.res[0] || vy >= k.res[1] || vz >= k.res[2]) return 0.0f;
-    const int64_t idx = vx + (int64_t)vy * k.res[0] + (int64_t)vz * k.res[0] * k.res[1];
+    const int64_t idx = sc_point_voxel(k, px, py, pz);
+    if (idx < 0) return 0.0f;
     ++nvis;
     if (MODE == TVAM_MODE_FWD) atomicAdd(&out[idx], w);
     else if (MODE == TVAM_MODE_ADJ) return w * (gin[idx] * k.inv_vol);
@@ -669,71 +478,30 @@ __global__ __launch_bounds__(256) void tvam_path_kernel(TvamConsts k, TvamTiles 
                                                         const int32_t* __restrict__ idxmap,
                                                         const float* __restrict__ gin, float* __restrict__ out,
                                                         unsigned long long* __restrict__ counter) {
-    const int spp = (int)tp.spp;
-    const int64_t per_angle = (int64_t)k.crop_y * k.crop_x;
-    const int64_t n = (int64_t)tp.n_shard * per_angle * spp;
-    const float st = k.sig_t, ss = k.sig_s, mj = k.majorant;
-    const bool has_sc = ss != 0.0f;
-    const int nsurf = k.vial_type == 0 ? 1 : 2;
+    const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * tp.spp;
+    const float st = k.sig_t;
+    const bool has_sc = k.sig_s != 0.0f;
+    const int nsurf = sc_nsurf(k);
     uint64_t nvis = 0;
+    const bool f32 = tvam_path_fits32(n);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t local = i / spp;
-        const int smp = (int)(i - local * spp);
-        float em = 1.0f;
-        int64_t act = local;
-        if (MODE == TVAM_MODE_FWD) {
-            const float p = pat[local];
-            if (p == 0.0f && k.skip_zero) continue;
-            em = p * k.wscale * k.inv_vol;
-        } else if (idxmap) {
-            act = idxmap[local];
-            if (act < 0) continue;
-        }
-        const int al = (int)(local / per_angle);
-        const int64_t pix = local - (int64_t)al * per_angle;
-        const int rowc = (int)(pix / k.crop_x), colc = (int)(pix - (int64_t)rowc * k.crop_x);
+        TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
+        float em;
+        int64_t act;
+        if (!tvam_path_gate<MODE>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
+        tvam_path_pixel(k, f32, ix);
         TvamPcg rng;
-        rng.seed(tp.seed, tvam_stream(k, idxmap, local, (uint32_t)spp, smp));
-        float jx = 0.5f, jy = 0.5f;
-        if (!k.regular) {
-            jx = rng.next_float();
-            jy = rng.next_float();
-        }
-        float c, sn;
-        if (k.sample_time) {  // common.py:101-104: time = (angle + u) / n_patterns
-            float time = (float)(k.a0 + al);
-            time = time + rng.next_float();
-            time = time / (float)k.n_patterns;
-            float alpha = TVAM_TWO_PI * time;
-            if (k.clockwise) alpha = -alpha;
-            c = cosf(alpha);
-            sn = sinf(alpha);
-        } else {
-            const float2 csv = tp.cs[al];
-            c = csv.x;
-            sn = csv.y;
-        }
-        (void)rng.next_float();  // aperture sample (projector.py:160)
-        (void)rng.next_float();
-        float xc, yc, ox, oy, oz, dx, dy;
-        tvam_ray_camera(k, k.crop_off_x + colc, k.crop_off_y + rowc, jx, jy, xc, yc);
-        tvam_ray_world(k, c, sn, xc, yc, ox, oy, oz, dx, dy);
-        float o2x, o2y, d2x, d2y, maxt, wgt;
-        if (!tvam_segment(k, ox, oy, oz, dx, dy, o2x, o2y, d2x, d2y, maxt, wgt)) continue;
-        for (int q = 0; q < (has_sc ? 5 : 4) * nsurf; ++q) (void)rng.next_float();  // RR, (medium), BSDF
-        float px = o2x, py = o2y, pz = oz, vx = d2x, vy = d2y, vz = 0.0f;
-        float att = wgt;
+        const TvamPathDraws dr = tvam_path_draws<true, true>(k, tp, ix.al, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), rng);
+        TvamPathSeg s;
+        if (!tvam_path_first_segment(k, ix, dr, s)) continue;
+        sc_skip_surface_draws(rng, nsurf, has_sc);
+        float px = s.o2x, py = s.o2y, pz = s.oz, vx = s.d2x, vy = s.d2y, vz = 0.0f;
+        float att = s.wgt;
         int depth = nsurf;
         float acc = 0.0f;
         for (int seg = 0;; ++seg) {
-            const float q = fminf(0.99f, att);
-            const float u_rr = rng.next_float();
-            if (depth > k.rr_depth) {  // Russian roulette (volume.py:182-185)
-                if (!(u_rr < q)) break;
-                att = att * (1.0f / q);
-            }
-            if (!(att != 0.0f)) break;
-            float tsi = maxt;
+            if (!sc_roulette(k, rng, depth, att)) break;
+            float tsi = s.maxt;
             if (seg > 0) {
                 tsi = sc_container_hit(k, px, py, pz, vx, vy, vz);
                 if (!(tsi < TVAM_INF)) break;
@@ -745,48 +513,22 @@ __global__ __launch_bounds__(256) void tvam_path_kernel(TvamConsts k, TvamTiles 
                 const float r = sc_dda<MODE>(k, px, py, pz, vx, vy, vz, tsi, em * att, out, gin, nvis);
                 if (MODE == TVAM_MODE_ADJ) acc = fmaf(att, r, acc);
             } else if (k.sensor_type == TVAM_SENSOR_RATIO) {
-                const float ratio = st / mj, keep = 1.0f - ratio;
-                float t = 0.0f, pk = 1.0f;
-                for (int it = 0; it < (1 << 20); ++it) {
-                    t = t + (-logf(1.0f - rng.next_float()) / mj);
-                    if (!(t < tsi)) break;
-                    const float w = att * pk * ratio;
+                sc_ratio_track(k, rng, tsi, att, [&](float t, float w) {
                     const float r = gp_point<MODE>(k, fmaf(vx, t, px), fmaf(vy, t, py), fmaf(vz, t, pz), em * w, out,
                                                    gin, nvis);
                     if (MODE == TVAM_MODE_ADJ) acc += r;  // w * grad * inv_vol (em = 1 in the adjoint)
-                    pk = pk * keep;
-                }
+                });
             } else if (!reached) {  // delta: the medium interaction ray(mei.t)
                 const float r = gp_point<MODE>(k, fmaf(vx, tmi, px), fmaf(vy, tmi, py), fmaf(vz, tmi, pz), em * att,
                                                out, gin, nvis);
                 if (MODE == TVAM_MODE_ADJ) acc += r;
             }
             if (reached) break;  // leaves the medium (transmission only, convex containers)
-            const float tr = expf(-tmi * st);
-            const float pdf = tr * st;
-            const float inv = pdf > 0.0f ? 1.0f / pdf : 0.0f;
-            float w = tr * inv;
-            w = w * ss;
-            (void)rng.next_float();  // phase next_1d
-            const float u1 = rng.next_float(), u2 = rng.next_float();
-            float wx, wy, wz;
-            sc_phase(k, vx, vy, vz, u1, u2, wx, wy, wz);
-            px = fmaf(vx, tmi, px);
-            py = fmaf(vy, tmi, py);
-            pz = fmaf(vz, tmi, pz);
-            vx = wx;
-            vy = wy;
-            vz = wz;
-            att = att * w;
-            ++depth;
-            if (depth >= k.max_depth) break;
+            if (!sc_medium_event(k, rng, tmi, px, py, pz, vx, vy, vz, att, depth)) break;
         }
         if (MODE == TVAM_MODE_ADJ && acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
     }
-    if (MODE == TVAM_MODE_COUNT) {
-        for (int off = 32; off > 0; off >>= 1) nvis += __shfl_down(nvis, off, 64);
-        if ((threadIdx.x & 63) == 0 && nvis) atomicAdd(counter, (unsigned long long)nvis);
-    }
+    if (MODE == TVAM_MODE_COUNT) tvam_count_reduce(nvis, counter);
 }
 
 __global__ __launch_bounds__(256) void tvam_scale_volumes_kernel(int64_t n, const float* __restrict__ vols,
@@ -901,9 +643,7 @@ hipError_t tvam_launch_surface_paths(int mode, const TvamConsts& k, const TvamTi
                                      const int32_t* idxmap, const float* gin, const float* vols, float* out,
                                      unsigned long long* counter, hipStream_t stream) {
     const int64_t n = (int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp;
-    int64_t g = (n + 255) / 256;
-    if (g > 262144) g = 262144;
-    if (g < 1) g = 1;
+    const unsigned g = tvam_grid_1d(n, 262144);
     // draws beyond the ray's own: a scattering medium (volume.py:159) or the ratio / delta sensor
     const bool scat = k.sig_s != 0.0f || k.sensor_type != TVAM_SENSOR_DDA;
 #define TVAM_SF_LAUNCH(M)                                                                                          \
@@ -926,9 +666,7 @@ hipError_t tvam_launch_general_paths(int mode, const TvamConsts& k, const TvamTi
                                      const int32_t* idxmap, const float* gin, float* out,
                                      unsigned long long* counter, hipStream_t stream) {
     const int64_t n = (int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp;
-    int64_t g = (n + 255) / 256;
-    if (g > 262144) g = 262144;
-    if (g < 1) g = 1;
+    const unsigned g = tvam_grid_1d(n, 262144);
     switch (mode) {
         case TVAM_MODE_FWD:
             hipLaunchKernelGGL(tvam_path_kernel<TVAM_MODE_FWD>, dim3((unsigned)g), dim3(256), 0, stream, k, t, pat,
@@ -1012,9 +750,7 @@ hipError_t tvam_launch_frozen(int mode, const TvamConsts& k, const TvamTiles& t,
                               hipStream_t stream) {
     if (!t.frozen || !t.frozen_n) return hipErrorInvalidValue;
     const int64_t n = (int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp;
-    int64_t g = (n + 255) / 256;
-    if (g > 4096) g = 4096;  // the list is short; a scan (list overflow) grid-strides
-    if (g < 1) g = 1;
+    const unsigned g = tvam_grid_1d(n, 4096);  // the list is short; a scan (list overflow) grid-strides
     switch (mode) {
         case TVAM_MODE_FWD:
             hipLaunchKernelGGL(tvam_frozen_kernel<TVAM_MODE_FWD>, dim3((unsigned)g), dim3(256), 0, stream, k, t, pat,
@@ -1035,9 +771,7 @@ hipError_t tvam_launch_scatter_paths(int mode, const TvamConsts& k, const TvamTi
                                      const int32_t* idxmap, const float* gin, float* out,
                                      unsigned long long* counter, hipStream_t stream) {
     const int64_t n = (int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp;
-    int64_t g = (n + 255) / 256;
-    if (g > 262144) g = 262144;
-    if (g < 1) g = 1;
+    const unsigned g = tvam_grid_1d(n, 262144);
     const TvamSegBuf none{};
     switch (mode) {
         case TVAM_MODE_FWD:

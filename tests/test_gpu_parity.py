@@ -71,38 +71,56 @@ CASES = [
     dict(N=24, A=12, zres=48, ray_fwd=True),
     dict(N=64, A=16, xyres=16),         # DMD 4x finer than the voxels: ray-driven forward
 ]
+# Jittered rays with a frozen axis (sensor.py:358; tvam_frozen_kernel): the smallest jittered scene of
+# this file (test_dot_product_gpu's) whose seed-0 rays hold some (5 of 368 640 in the oracle; seeds
+# 1 and 2 hold none).  A lost frozen ray would leave one of its pixel's 4 samples out of the
+# gradient (~0.25 relative on that entry) and its voxels' doses off by ~5e-3 (estimated from the
+# ray counts): the bounds below catch either.
+FROZEN_CASE = dict(N=48, A=40, regular=False, spp=4, seed=0, frozen=True)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
+@pytest.mark.parametrize("case", CASES + [FROZEN_CASE], ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
 def test_forward_matches_oracle(oracle, case):
     case = dict(case)
     spp = case.get("spp", 1)
+    seed, frozen = case.pop("seed", 5), case.pop("frozen", False)
     d = make(**case)
     n = d.n_patterns * d.crop_y * d.crop_x
     pat = np.random.default_rng(0).uniform(0.0, 0.1, n).astype(np.float32)
-    ref, visits = oracle.forward(d, pat, spp=spp, seed=5, nthreads=8)
-    got, proj = gpu_forward(d, pat, spp=spp, seed=5)
+    oracle.frozen_axes()  # reset the count
+    ref, visits = oracle.forward(d, pat, spp=spp, seed=seed, nthreads=8)
+    if frozen:  # (the case cannot pass while testing nothing)
+        assert oracle.frozen_axes() >= 1
+    got, proj = gpu_forward(d, pat, spp=spp, seed=seed)
+    if frozen:
+        assert proj.tile_stats()["frozen"] >= 1
     # planar path: regular sampling and every row's vial-entry offset row-independent (|z| <= 0.7 r)
     assert proj.planar == (case.get("regular", True) and case.get("planar", True) and 5.0 <= 0.7 * case.get("r", 8.0))
     assert proj.planar_forward == (proj.planar and not case.get("ray_fwd") and case.get("xyres") is None)
     assert rel_l2(got, ref) < RTOL_L2
     assert np.max(np.abs(got - ref)) <= 1e-4 * np.max(np.abs(ref)) + 1e-7
-    hv = proj.count_visits(spp, 5)
+    hv = proj.count_visits(spp, seed)
     assert abs(hv - visits) <= max(2, 1e-4 * visits)
 
 
-@pytest.mark.parametrize("case", CASES[:5] + CASES[7:] + [dict(N=32, A=16, regular=False, spp=2)],
+@pytest.mark.parametrize("case", CASES[:5] + CASES[7:] + [dict(N=32, A=16, regular=False, spp=2), FROZEN_CASE],
                          ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
 def test_adjoint_matches_oracle(oracle, case):
     case = dict(case)
     spp = case.get("spp", 1)
+    seed, frozen = case.pop("seed", 9), case.pop("frozen", False)
     d = make(**case)
     N = d.film_res[0]
     n = d.n_patterns * d.crop_y * d.crop_x
     G = np.random.default_rng(1).uniform(-1, 1, (d.film_res[2], d.film_res[1], N)).astype(np.float32)
-    ref, _ = oracle.adjoint(d, G, spp=spp, seed=9, nthreads=8)
+    oracle.frozen_axes()  # reset the count
+    ref, _ = oracle.adjoint(d, G, spp=spp, seed=seed, nthreads=8)
+    if frozen:
+        assert oracle.frozen_axes() >= 1
     proj = Projection(d, "cuda:0")
-    g = proj.adjoint(torch.as_tensor(G, device="cuda:0"), n, None, spp, 9).cpu().numpy()
+    g = proj.adjoint(torch.as_tensor(G, device="cuda:0"), n, None, spp, seed).cpu().numpy()
+    if frozen:
+        assert proj.tile_stats()["frozen"] >= 1
     assert rel_l2(g, ref) < RTOL_L2
 
 
