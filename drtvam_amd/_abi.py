@@ -203,6 +203,7 @@ EXPORTS = {
     ),
     "tvam_last_error": (ctypes.c_char_p, []),
     "tvam_abi_version": (ctypes.c_int, []),
+    "tvam_device_bytes": (ctypes.c_int64, []),
 }
 
 _lib = None

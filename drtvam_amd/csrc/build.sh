@@ -14,10 +14,11 @@ flags=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC
        -Wall -Wno-unused-function -I"$here/../../include")
 pids=()
 objs=()
-for src in tvam_plan tvam_kernels tvam_planar tvam_adjlist tvam_vec tvam_scatter tvam_radon tvam_cone tvam_corner; do
-  "$HIPCC" "${flags[@]}" ${TVAM_CXXFLAGS:-} -c "$here/$src.hip" -o "$objdir/$src.o" &
+for src in "$here"/*.hip; do  # every translation unit (the glob sorts)
+  obj="$objdir/$(basename "$src" .hip).o"
+  "$HIPCC" "${flags[@]}" ${TVAM_CXXFLAGS:-} -c "$src" -o "$obj" &
   pids+=($!)
-  objs+=("$objdir/$src.o")
+  objs+=("$obj")
 done
 fail=0
 for pid in "${pids[@]}"; do wait "$pid" || fail=1; done

@@ -383,29 +383,28 @@ hipError_t tvam_build_adj_lists(const TvamConsts& k, TvamPlanar& pl, const TvamT
     if ((e = hipMemcpy(off.data(), t.slot_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
         return e;
     const int64_t nslots = off[(size_t)ntiles];
-    uint32_t *d_cnt = nullptr, *d_ent = nullptr;
-    if ((e = hipMalloc((void**)&d_cnt, (size_t)std::max<int64_t>(nslots, 1) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void**)&d_ent, (size_t)std::max<int64_t>(nslots, 1) * sizeof(uint32_t))) != hipSuccess) {
-        (void)hipFree(d_cnt);
+    TvamDevBuf<uint32_t> d_cnt, d_ent;
+    if ((e = d_cnt.alloc((size_t)std::max<int64_t>(nslots, 1))) != hipSuccess ||
+        (e = d_ent.alloc((size_t)std::max<int64_t>(nslots, 1))) != hipSuccess)
         return e;
-    }
     int64_t maxn = 0;
     for (int i = 0; i < ntiles; ++i) maxn = std::max(maxn, off[(size_t)i + 1] - off[(size_t)i]);
     if (maxn > 0) {
         dim3 grid((unsigned)((maxn + 255) / 256), (unsigned)ntiles);
         if (w2)
-            hipLaunchKernelGGL((tvam_adjl_count_kernel<true>), grid, dim3(256), 0, stream, k, pl, t, d_cnt, d_ent);
+            hipLaunchKernelGGL((tvam_adjl_count_kernel<true>), grid, dim3(256), 0, stream, k, pl, t, d_cnt.get(),
+                               d_ent.get());
         else
-            hipLaunchKernelGGL((tvam_adjl_count_kernel<false>), grid, dim3(256), 0, stream, k, pl, t, d_cnt, d_ent);
+            hipLaunchKernelGGL((tvam_adjl_count_kernel<false>), grid, dim3(256), 0, stream, k, pl, t, d_cnt.get(),
+                               d_ent.get());
     }
     std::vector<uint32_t> cnt((size_t)nslots), ent((size_t)nslots);
     if ((e = hipGetLastError()) == hipSuccess) e = hipStreamSynchronize(stream);
     if (e == hipSuccess && nslots > 0 &&
-        ((e = hipMemcpy(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess ||
-         (e = hipMemcpy(ent.data(), d_ent, ent.size() * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess)) {
-    }
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_ent);
+        (e = hipMemcpy(cnt.data(), d_cnt.get(), cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost)) == hipSuccess)
+        e = hipMemcpy(ent.data(), d_ent.get(), ent.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)d_cnt.reset();  // (before the lists are allocated)
+    (void)d_ent.reset();
     if (e != hipSuccess) return e;
     static const int LG[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                   {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
@@ -491,44 +490,30 @@ hipError_t tvam_build_adj_lists(const TvamConsts& k, TvamPlanar& pl, const TvamT
     // lanes start up to 15 x steps before their entry voxel
     if (nslots >= (1 << 27)) return hipErrorOutOfMemory;  // slot | delay << 27
     pl.adjl_slack = (int32_t)(16 * (maxlen + 16));
-    int32_t *d_cslot = nullptr, *d_cgrp = nullptr;
-    auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t r = hipMalloc(dst, std::max<size_t>(bytes, 16));
-        if (r == hipSuccess && bytes) r = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-        return r;
-    };
-    if ((e = up((void**)&bufs.gchunk, gchunk.data(), gchunk.size() * sizeof(int32_t))) != hipSuccess ||
-        (e = up((void**)&bufs.glist, glist.data(), glist.size() * sizeof(int32_t))) != hipSuccess ||
-        (e = up((void**)&bufs.coff, coff.data(), coff.size() * sizeof(int64_t))) != hipSuccess ||
-        (e = up((void**)&d_cslot, cslot.data(), cslot.size() * sizeof(int32_t))) != hipSuccess ||
-        (e = up((void**)&d_cgrp, cgrp.data(), cgrp.size() * sizeof(int32_t))) != hipSuccess ||
-        (e = hipMalloc((void**)&bufs.hdr, std::max<size_t>(hbytes, 16))) != hipSuccess ||
-        (e = hipMalloc((void**)&bufs.w, std::max<size_t>(wbytes, 16))) != hipSuccess) {
-        (void)hipFree(d_cslot);
-        (void)hipFree(d_cgrp);
+    TvamDevBuf<int32_t> d_cslot, d_cgrp;
+    if ((e = bufs.gchunk.upload(gchunk)) != hipSuccess || (e = bufs.glist.upload(glist)) != hipSuccess ||
+        (e = bufs.coff.upload(coff)) != hipSuccess || (e = d_cslot.upload(cslot)) != hipSuccess ||
+        (e = d_cgrp.upload(cgrp)) != hipSuccess ||
+        (e = bufs.hdr.alloc(std::max<size_t>((size_t)nchunks * 64, 1))) != hipSuccess ||
+        (e = bufs.w.alloc(std::max<size_t>((size_t)coff.back() * 64, 1))) != hipSuccess)
         return e;
-    }
-    pl.adjl_gchunk = bufs.gchunk;
-    pl.adjl_glist = bufs.glist;
+    pl.adjl_gchunk = bufs.gchunk.get();
+    pl.adjl_glist = bufs.glist.get();
     pl.adjl_nlist = (int32_t)glist.size();
-    pl.adjl_coff = bufs.coff;
-    pl.adjl_hdr = bufs.hdr;
-    pl.adjl_w = bufs.w;
+    pl.adjl_coff = bufs.coff.get();
+    pl.adjl_hdr = bufs.hdr.get();
+    pl.adjl_w = bufs.w.get();
     pl.adjl_ngroups = ntiles * 4 * parts;
     pl.adjl_parts = parts;
     if (nchunks > 0) {
         const unsigned nb = (unsigned)((nchunks * 64 + 255) / 256);
         if (w2)
-            hipLaunchKernelGGL((tvam_adjl_fill_kernel<true>), dim3(nb), dim3(256), 0, stream, k, pl, t, nchunks, d_cslot,
-                               d_cgrp, bufs.hdr, bufs.w);
+            hipLaunchKernelGGL((tvam_adjl_fill_kernel<true>), dim3(nb), dim3(256), 0, stream, k, pl, t, nchunks,
+                               d_cslot.get(), d_cgrp.get(), bufs.hdr.get(), bufs.w.get());
         else
-            hipLaunchKernelGGL((tvam_adjl_fill_kernel<false>), dim3(nb), dim3(256), 0, stream, k, pl, t, nchunks, d_cslot,
-                               d_cgrp, bufs.hdr, bufs.w);
+            hipLaunchKernelGGL((tvam_adjl_fill_kernel<false>), dim3(nb), dim3(256), 0, stream, k, pl, t, nchunks,
+                               d_cslot.get(), d_cgrp.get(), bufs.hdr.get(), bufs.w.get());
     }
     if ((e = hipGetLastError()) == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_cslot);
-    (void)hipFree(d_cgrp);
-    bufs.bytes = wbytes + hbytes;
-    bufs.visits_padded = coff.back() * 256;
     return e;
 }

@@ -1,5 +1,7 @@
-// tvam_internal.h — plan layout and kernel launchers shared by tvam_plan.hip
-// and tvam_kernels.hip (not part of the public ABI).
+// tvam_internal.h — the structs passed to kernels, the plan's device buffers and the kernel
+// launchers that cross translation units (not part of the public ABI).  Host side: tvam_plan.hip
+// builds a plan (tvam_plan.h), tvam_calls.hip runs its per-call entry points; each launcher lives
+// beside its kernels.  Device memory is owned by TvamDevBuf (tvam_devbuf.h) alone.
 #pragma once
 
 // Row pitch (voxels) of the per-ray tile kernels' LDS tile (tile + 1-voxel guard band): odd, so
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "tvam_common.h"
+#include "tvam_devbuf.h"
 #include "../../include/tvam.h"
 
 // A tuning knob: the environment variable `name` under TVAM_EXPERIMENTAL=1 (logged), else `def`
@@ -120,13 +123,10 @@ struct TvamPlanar {
 
 // Device buffers of the visit lists (owned by the plan).
 struct TvamAdjListBufs {
-    int32_t* gchunk = nullptr;
-    int32_t* glist = nullptr;
-    int64_t* coff = nullptr;
-    int4* hdr = nullptr;
-    float4* w = nullptr;
-    size_t bytes = 0;
-    int64_t visits_padded = 0;
+    TvamDevBuf<int32_t> gchunk, glist;
+    TvamDevBuf<int64_t> coff;
+    TvamDevBuf<int4> hdr;
+    TvamDevBuf<float4> w;
 };
 size_t tvam_adjl_lds(const TvamPlanar& pl, const TvamTiles& t, int Z);
 hipError_t tvam_build_adj_lists(const TvamConsts& k, TvamPlanar& pl, const TvamTiles& t, int parts, size_t max_bytes,
@@ -201,12 +201,9 @@ struct TvamSegBuf {
 // the scan, the bin fill and the sort, rescales the records' weights to the new pattern and
 // marches.  c.z of each record holds the path attenuation for that rescale.
 struct TvamBinChunk {
-    float4* r = nullptr;          // [3 * cap_slots] records
-    int64_t cap_slots = 0;
-    uint32_t* vals = nullptr;     // [cap_vals] sorted segment slots, or counting-sort entries (ws)
-    int64_t cap_vals = 0;
-    uint32_t* bstart = nullptr;   // [nbricks + 1]
-    int64_t cap_bricks = 0;
+    TvamDevBuf<float4> r;         // [TVAM_REC_F4 * slots] records
+    TvamDevBuf<uint32_t> vals;    // sorted segment slots, or counting-sort entries (ws)
+    TvamDevBuf<uint32_t> bstart;  // [nbricks + 1]
     uint32_t total = 0;
     bool valid = false;
     bool ws = false;              // vals are tvam_bin_fill2_kernel entries (slot | class << 28)
@@ -214,21 +211,22 @@ struct TvamBinChunk {
 
 // Scratch of the binned forward (owned by the plan, grown on demand).
 struct TvamBinScratch {
-    TvamSegBuf sb;
+    // the chunk's segment records (TvamSegBuf r, m, wmax, bad) and the exclusive scan of m;
+    // r, m and off hold cap_slots slots
+    TvamDevBuf<float4> r;
+    TvamDevBuf<uint32_t> m, wmax, bad;
+    TvamDevBuf<uint32_t> off;     // [cap_slots + 1]
     int64_t cap_slots = 0;
-    uint32_t* off = nullptr;      // [cap_slots + 1] exclusive scan of m
-    uint32_t* keys[2] = {nullptr, nullptr};
-    uint32_t* vals[2] = {nullptr, nullptr};
+    // entry arrays: keys[0], vals[1] and part hold cap_entries entries; the radix sort's second
+    // buffers keys[1] and vals[0] hold cap_entries2
+    TvamDevBuf<uint32_t> keys[2], vals[2];
+    TvamDevBuf<float> part;       // adjoint partial of each entry
     int64_t cap_entries = 0, cap_entries2 = 0;
-    uint32_t* bstart = nullptr;   // [nbricks + 1]
-    int32_t cap_bricks = 0;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
+    TvamDevBuf<uint32_t> bstart;  // [nbricks + 1]
+    TvamDevBuf<char> temp;        // hipcub scratch
     int acc_float = 0;            // 1: float LDS adds instead of int64 fixed point (TVAM_BIN_FLOAT)
-    float* part = nullptr;        // [cap_entries] adjoint partial of each entry
-    uint32_t* hist = nullptr;     // [nbricks * G + 1] writer counts per (brick, workgroup), then their scan
-    uint32_t* hbase = nullptr;
-    int64_t cap_hist = 0;
+    TvamDevBuf<uint32_t> hist;    // [nbricks * G + 1] writer counts per (brick, workgroup), then their scan
+    TvamDevBuf<uint32_t> hbase;   // (as large as hist)
     // forward bin cache (TvamBinChunk), keyed on the call's constants, seed, spp and chunking
     std::vector<TvamBinChunk> fc;
     bool fc_key = false;
@@ -238,13 +236,18 @@ struct TvamBinScratch {
     // last call's chunking (tvam_plan_bin_stats): chunks, chunks served from the cache,
     // chunks stored into it, brick entries sorted, paths per chunk
     int64_t st[5] = {0, 0, 0, 0, 0};
-    // the bin-fill count check (sb.bad, cumulative since the scratch was allocated) is read lazily:
+    // the bin-fill count check (bad, cumulative since the scratch was allocated) is read lazily:
     // each binned call ends with an async copy into pinned host memory and an event, and the next
     // call checks the copy once its event has completed -- no stream synchronisation on the hot path
     uint32_t* bad_host = nullptr;
     hipEvent_t bad_ev = nullptr;
     bool bad_pending = false;
-    int64_t temp_cap() const { return (int64_t)temp_bytes; }
+    // the kernels' view of the record buffers (the caller sets the chunk's p0, p1, slots, adj)
+    TvamSegBuf seg() const {
+        TvamSegBuf sb{};
+        sb.r = r.get(), sb.m = m.get(), sb.wmax = wmax.get(), sb.bad = bad.get();
+        return sb;
+    }
 };
 
 hipError_t tvam_launch_tiles(int mode, const TvamConsts& k, const TvamTiles& t, size_t lds_bytes,
@@ -267,6 +270,7 @@ typedef void (*TvamRecWriter)(const TvamConsts& k, const TvamTiles& t, const flo
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
                                hipStream_t stream, TvamRecWriter writer = nullptr);
+// the scratch back to its initial state: its event and pinned word here, the device memory with its owners
 void tvam_bin_scratch_free(TvamBinScratch& s);
 
 // Surface-aware films (film_channels 2): every path's medium segment cut at the
@@ -325,44 +329,3 @@ hipError_t tvam_launch_gather(const TvamConsts& k, const float* dense, const uin
                               uint64_t n, float* out, hipStream_t stream);
 
 #define TVAM_MAX_PROBES 8
-// target: f32 (> 0 = object), or mask != nullptr: its bit mask (tvam_launch_target_mask) read from bit mbit0
-hipError_t tvam_launch_loss_probes(const float* dose, const float* ddose, const float* alphas, int na,
-                                   const float* target, const uint32_t* mask, uint64_t mbit0, uint64_t n, int K,
-                                   float tl, float tu, float w_object, float w_void, float w_limit, float scale,
-                                   double* out, hipStream_t stream);
-hipError_t tvam_launch_loss_threshold(const float* dose, const float* ddose, float alpha, const float* target,
-                                      const uint32_t* mask, uint64_t mbit0, uint64_t n, int K, float tl, float tu,
-                                      float w_object, float w_void, float w_limit, float scale, double* out,
-                                      float* grad, hipStream_t stream);
-hipError_t tvam_launch_target_mask(const float* target, uint64_t n, uint32_t* mask, hipStream_t stream);
-
-// Fused L-BFGS vector kernels (tvam_vec.hip).
-hipError_t tvam_launch_lbfgs_history(uint64_t n, const float* p, const float* p_old, const float* g,
-                                     const float* g_old, int h, const float* const* S, const float* const* Y,
-                                     float* s_new, float* y_new, double* work, double* dots, hipStream_t stream,
-                                     uint64_t nseg = 0, uint64_t seg_len = 0, uint64_t seg_stride = 0,
-                                     uint64_t seg_off = 0);
-hipError_t tvam_launch_lbfgs_direction(uint64_t n, const float* g, int h, const float* const* S,
-                                       const float* const* Y, float cg, const float* cs, const float* cy, float* d,
-                                       hipStream_t stream);
-hipError_t tvam_launch_lbfgs_coef(int h, int is_new, int first, const int* order, const double* dots, double* gram,
-                                  float* coef, double* gdz, hipStream_t stream);
-hipError_t tvam_launch_lbfgs_direction_dev(uint64_t n, const float* g, int h, const float* const* S,
-                                           const float* const* Y, const float* coef, float* d, hipStream_t stream,
-                                           uint64_t nseg = 0, uint64_t seg_len = 0, uint64_t seg_stride = 0,
-                                           uint64_t seg_off = 0);
-hipError_t tvam_launch_axpy_clamp(uint64_t n, const float* p, float alpha, const float* d, float lo, float* out,
-                                  hipStream_t stream, const float* alpha_dev = nullptr, float* s_out = nullptr);
-hipError_t tvam_launch_armijo(int nprobe, double a0, const double* probes, const double* loss_dev, double loss_host,
-                              double loss_div, const double* gdz, double c1, float* alpha, double* report,
-                              hipStream_t stream);
-// First-order optimiser updates (tvam_vec.hip); the scalars already rounded to fp32 (c = fl32(1 - beta)).
-hipError_t tvam_launch_sgd_step(uint64_t n, float* p, const float* g, float* s, float lr, float mu, bool mask,
-                                float lo, hipStream_t stream);
-hipError_t tvam_launch_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1,
-                                 float c1, float b2, float c2, float eps, bool mask, float lo, hipStream_t stream);
-hipError_t tvam_launch_adam_moments(uint64_t n, const float* g, float* m, float* v, float b1, float c1, float b2,
-                                    float c2, bool mask, double* work, double* S, hipStream_t stream);
-hipError_t tvam_launch_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
-                                  const double* count, float lr_t, float eps, bool mask, float lo,
-                                  hipStream_t stream);

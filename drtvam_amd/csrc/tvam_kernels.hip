@@ -17,7 +17,7 @@
 //  * The march is resumed at the tile entry in closed form: the reference
 //    DDA steps axis a at t_start + dtm0[a] + n*ts[a], so the voxel index and
 //    dtmax at any time follow without marching the skipped part.
-#include "tvam_internal.h"
+#include "tvam_plan.h"
 #include "tvam_path.h"
 
 #define TVAM_BLOCK 256
@@ -749,7 +749,7 @@ __global__ __launch_bounds__(256) void tvam_target_mask_kernel(const float* __re
     }
 }
 
-hipError_t tvam_launch_target_mask(const float* target, uint64_t n, uint32_t* mask, hipStream_t stream) {
+static hipError_t tvam_launch_target_mask(const float* target, uint64_t n, uint32_t* mask, hipStream_t stream) {
     const uint64_t nw = (n + 31) / 32;
     unsigned g = (unsigned)((nw + 255) / 256);
     if (g > 4096) g = 4096;
@@ -886,10 +886,11 @@ static bool tvam_al16(const void* a, const void* b, const void* c) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
-hipError_t tvam_launch_loss_probes(const float* dose, const float* ddose, const float* alphas, int na,
-                                   const float* target, const uint32_t* mask, uint64_t mbit0, uint64_t n, int K,
-                                   float tl, float tu, float w_object, float w_void, float w_limit, float scale,
-                                   double* out, hipStream_t stream) {
+// target: f32 (> 0 = object), or mask != nullptr: its bit mask (tvam_launch_target_mask) read from bit mbit0
+static hipError_t tvam_launch_loss_probes(const float* dose, const float* ddose, const float* alphas, int na,
+                                          const float* target, const uint32_t* mask, uint64_t mbit0, uint64_t n,
+                                          int K, float tl, float tu, float w_object, float w_void, float w_limit,
+                                          float scale, double* out, hipStream_t stream) {
     TvamProbeAlphas al{};
     for (int j = 0; j < na; ++j) al.a[j] = alphas[j];
     const bool v4 = tvam_al16(dose, ddose, mask ? nullptr : target) && (!mask || mbit0 % 4 == 0);
@@ -918,7 +919,7 @@ hipError_t tvam_launch_loss_probes(const float* dose, const float* ddose, const 
     return hipGetLastError();
 }
 
-hipError_t tvam_launch_loss_threshold(const float* dose, const float* ddose, float alpha, const float* target,
+static hipError_t tvam_launch_loss_threshold(const float* dose, const float* ddose, float alpha, const float* target,
                                       const uint32_t* mask, uint64_t mbit0, uint64_t n, int K, float tl, float tu,
                                       float w_object, float w_void, float w_limit, float scale, double* out,
                                       float* grad, hipStream_t stream) {
@@ -947,4 +948,57 @@ hipError_t tvam_launch_loss_threshold(const float* dose, const float* ddose, flo
 #undef TVAM_LOSS_K
 #undef TVAM_LOSS
     return hipGetLastError();
+}
+
+// The extern "C" boundary of these kernels (include/tvam.h).
+extern "C" int tvam_loss_threshold(const float* dose, const float* ddose, float alpha, const float* target, uint64_t n,
+                                   int32_t K, float tl, float tu, float w_object, float w_void, float w_limit,
+                                   float scale, double* out, float* grad, void* stream) {
+    if (!dose || !target || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (K < 1 || K > 16) return tvam_fail(TVAM_ERR_UNSUPPORTED, "ThresholdedLoss: integer K in [1, 16] required on the GPU path");
+    hipError_t e = tvam_launch_loss_threshold(dose, ddose, alpha, target, nullptr, 0, n, K, tl, tu, w_object, w_void,
+                                              w_limit, scale, out, grad, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "loss launch");
+}
+
+extern "C" int tvam_target_mask(const float* target, uint64_t n, uint32_t* mask, void* stream) {
+    if (!target || !mask) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    hipError_t e = tvam_launch_target_mask(target, n, mask, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "target mask launch");
+}
+
+extern "C" int tvam_loss_threshold_mask(const float* dose, const float* ddose, float alpha, const uint32_t* mask,
+                                        uint64_t mask_bit0, uint64_t n, int32_t K, float tl, float tu, float w_object,
+                                        float w_void, float w_limit, float scale, double* out, float* grad,
+                                        void* stream) {
+    if (!dose || !mask || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (K < 1 || K > 16) return tvam_fail(TVAM_ERR_UNSUPPORTED, "ThresholdedLoss: integer K in [1, 16] required on the GPU path");
+    hipError_t e = tvam_launch_loss_threshold(dose, ddose, alpha, nullptr, mask, mask_bit0, n, K, tl, tu, w_object,
+                                              w_void, w_limit, scale, out, grad, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "loss launch");
+}
+
+extern "C" int tvam_loss_threshold_probes_mask(const float* dose, const float* ddose, const float* alphas,
+                                               int32_t n_alpha, const uint32_t* mask, uint64_t mask_bit0, uint64_t n,
+                                               int32_t K, float tl, float tu, float w_object, float w_void,
+                                               float w_limit, float scale, double* out, void* stream) {
+    if (!dose || !ddose || !alphas || !mask || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (n_alpha < 1 || n_alpha > TVAM_MAX_PROBES)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_loss_threshold_probes_mask: 1 <= n_alpha <= 8");
+    if (K < 1 || K > 16) return tvam_fail(TVAM_ERR_UNSUPPORTED, "ThresholdedLoss: integer K in [1, 16] required on the GPU path");
+    hipError_t e = tvam_launch_loss_probes(dose, ddose, alphas, n_alpha, nullptr, mask, mask_bit0, n, K, tl, tu,
+                                           w_object, w_void, w_limit, scale, out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "loss probes launch");
+}
+
+extern "C" int tvam_loss_threshold_probes(const float* dose, const float* ddose, const float* alphas, int32_t n_alpha,
+                                          const float* target, uint64_t n, int32_t K, float tl, float tu,
+                                          float w_object, float w_void, float w_limit, float scale, double* out,
+                                          void* stream) {
+    if (!dose || !ddose || !alphas || !target || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (n_alpha < 1 || n_alpha > TVAM_MAX_PROBES) return tvam_fail(TVAM_ERR_INVALID, "tvam_loss_threshold_probes: 1 <= n_alpha <= 8");
+    if (K < 1 || K > 16) return tvam_fail(TVAM_ERR_UNSUPPORTED, "ThresholdedLoss: integer K in [1, 16] required on the GPU path");
+    hipError_t e = tvam_launch_loss_probes(dose, ddose, alphas, n_alpha, target, nullptr, 0, n, K, tl, tu, w_object,
+                                           w_void, w_limit, scale, out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "loss probes launch");
 }

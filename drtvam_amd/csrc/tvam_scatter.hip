@@ -714,18 +714,13 @@ hipError_t tvam_launch_volumes(const TvamConsts& k, uint32_t sample_count, float
             box[6 * (size_t)i + 3 + a] = fmaxf(fmaxf(t[a], t[3 + a]), t[6 + a]) + grow;
         }
     }
-    float* d_box = nullptr;
-    if ((e = hipMalloc((void**)&d_box, box.size() * sizeof(float))) != hipSuccess) return e;
-    if ((e = hipMemcpy(d_box, box.data(), box.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) {
-        (void)hipFree(d_box);
-        return e;
-    }
+    TvamDevBuf<float> d_box;
+    if ((e = d_box.upload(box)) != hipSuccess) return e;
     const int64_t V = (int64_t)k.res[0] * k.res[1] * k.res[2];
     const unsigned g = (unsigned)std::min<int64_t>(std::max<int64_t>((V + 255) / 256, 1), 1 << 20);
-    hipLaunchKernelGGL(tvam_volume_kernel, dim3(g), dim3(256), 0, stream, k, mb0, mb1, sample_count, d_box, volumes);
+    hipLaunchKernelGGL(tvam_volume_kernel, dim3(g), dim3(256), 0, stream, k, mb0, mb1, sample_count, d_box.get(), volumes);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_box);
     return e;
 }
 
@@ -1296,39 +1291,9 @@ __global__ __launch_bounds__(256) void tvam_bin_reweight_kernel(TvamConsts k, Tv
     sc_block_max(wmax, sb.wmax);
 }
 
-template <typename T>
-hipError_t grow(T** p, int64_t& cap, int64_t need) {
-    if (need <= cap) return hipSuccess;
-    (void)hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void**)p, (size_t)need * sizeof(T));
-    if (e == hipSuccess) cap = need;
-    return e;
-}
-
 }  // namespace
 
 void tvam_bin_scratch_free(TvamBinScratch& s) {
-    (void)hipFree(s.sb.r);
-    (void)hipFree(s.sb.m);
-    (void)hipFree(s.sb.wmax);
-    (void)hipFree(s.sb.bad);
-    (void)hipFree(s.off);
-    for (int i = 0; i < 2; ++i) {
-        (void)hipFree(s.keys[i]);
-        (void)hipFree(s.vals[i]);
-    }
-    (void)hipFree(s.bstart);
-    (void)hipFree(s.temp);
-    (void)hipFree(s.part);
-    (void)hipFree(s.hist);
-    (void)hipFree(s.hbase);
-    for (auto& c : s.fc) {
-        (void)hipFree(c.r);
-        (void)hipFree(c.vals);
-        (void)hipFree(c.bstart);
-    }
     if (s.bad_ev) (void)hipEventSynchronize(s.bad_ev);
     (void)hipHostFree(s.bad_host);
     if (s.bad_ev) (void)hipEventDestroy(s.bad_ev);
@@ -1394,23 +1359,19 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         const int keep_float = s.acc_float;
         tvam_bin_scratch_free(s);
         s.acc_float = keep_float;
-        if ((e = hipMalloc((void**)&s.sb.r, TVAM_REC_F4 * nsl * sizeof(float4))) != hipSuccess ||
-            (e = hipMalloc((void**)&s.sb.m, (nsl + 1) * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&s.off, (nsl + 1) * sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&s.sb.wmax, sizeof(uint32_t))) != hipSuccess ||
-            (e = hipMalloc((void**)&s.sb.bad, sizeof(uint32_t))) != hipSuccess ||
+        if ((e = s.r.alloc(TVAM_REC_F4 * (size_t)nsl)) != hipSuccess || (e = s.m.alloc((size_t)nsl + 1)) != hipSuccess ||
+            (e = s.off.alloc((size_t)nsl + 1)) != hipSuccess || (e = s.wmax.alloc(1)) != hipSuccess ||
+            (e = s.bad.alloc(1)) != hipSuccess ||
             (e = hipHostMalloc((void**)&s.bad_host, sizeof(uint32_t))) != hipSuccess ||
             (e = hipEventCreateWithFlags(&s.bad_ev, hipEventDisableTiming)) != hipSuccess)
             return e;
         *s.bad_host = 0;
         // the fill walks that disagreed with the record writer's brick counts, summed over the calls
         // (bin stats [7])
-        if ((e = hipMemsetAsync(s.sb.bad, 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(s.bad.get(), 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
         s.cap_slots = nsl;
     }
-    int64_t capb = s.cap_bricks;
-    if ((e = grow(&s.bstart, capb, (int64_t)nbricks + 1)) != hipSuccess) return e;
-    s.cap_bricks = (int32_t)capb;
+    if ((e = s.bstart.grow((size_t)nbricks + 1)) != hipSuccess) return e;
     // forward bin cache: dense pattern sets only (a sparse set's streams follow the set), and not
     // with skip_zero (then the paths depend on the pattern); TVAM_BIN_CACHE=0 turns it off
     const bool cacheable = !adj && !idxmap && !k.skip_zero && tvam_knob("TVAM_BIN_CACHE", 1) != 0;
@@ -1461,7 +1422,7 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         const int64_t p1 = std::min(npaths, p0 + chunk);
         const int64_t ns = (p1 - p0) * slots;
         ++s.st[0];
-        TvamSegBuf sb = s.sb;
+        TvamSegBuf sb = s.seg();
         sb.p0 = p0;
         sb.p1 = p1;
         sb.slots = slots;
@@ -1472,42 +1433,27 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
             ++s.st[1];
             s.st[3] += cc->total;
             if (cc->total == 0) continue;
-            sb.r = cc->r;
+            sb.r = cc->r.get();
             int64_t g = std::min<int64_t>((ns + 255) / 256, 8192);
             hipLaunchKernelGGL(tvam_bin_reweight_kernel, dim3((unsigned)g), dim3(256), 0, stream, k, sb, spp, pat);
-            march_fwd(sb, cc->vals, cc->bstart, cc->ws);
+            march_fwd(sb, cc->vals.get(), cc->bstart.get(), cc->ws);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             continue;
         }
-        if (cc && cc->cap_slots < nsl) {
-            (void)hipFree(cc->r);
-            cc->r = nullptr;
-            cc->cap_slots = 0;
-            if (room(TVAM_REC_F4 * (size_t)nsl * sizeof(float4)) &&
-                hipMalloc((void**)&cc->r, TVAM_REC_F4 * (size_t)nsl * sizeof(float4)) == hipSuccess)
-                cc->cap_slots = nsl;
-            else
-                cc->r = nullptr;
+        if (cc && cc->r.capacity() < TVAM_REC_F4 * (size_t)nsl) {
+            (void)cc->r.reset();
+            if (room(TVAM_REC_F4 * (size_t)nsl * sizeof(float4))) (void)cc->r.alloc(TVAM_REC_F4 * (size_t)nsl);
         }
-        if (cc && !cc->r) cc = nullptr;  // no room: this chunk runs from the scratch
-        if (cc) sb.r = cc->r;
+        if (cc && !cc->r.get()) cc = nullptr;  // no room: this chunk runs from the scratch
+        if (cc) sb.r = cc->r.get();
         if ((e = hipMemsetAsync(sb.m, 0, (ns + 1) * sizeof(uint32_t), stream)) != hipSuccess) return e;
         int64_t g = std::min<int64_t>((p1 - p0 + 255) / 256, 262144);
         const int G = csort ? (int)std::min<int64_t>((p1 - p0 + 255) / 256, 2048) : 0;
         const int64_t nh = (int64_t)nbricks * G + 1;  // per-(brick, workgroup) counts + the total
         if (csort) {
-            if (nh > s.cap_hist) {
-                (void)hipFree(s.hist);
-                (void)hipFree(s.hbase);
-                s.hist = s.hbase = nullptr;
-                s.cap_hist = 0;
-                if ((e = hipMalloc((void**)&s.hist, nh * sizeof(uint32_t))) != hipSuccess ||
-                    (e = hipMalloc((void**)&s.hbase, nh * sizeof(uint32_t))) != hipSuccess)
-                    return e;
-                s.cap_hist = nh;
-            }
-            if ((e = hipMemsetAsync(s.hist + (nh - 1), 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
-            sb.hist = s.hist;
+            if ((e = s.hist.grow((size_t)nh)) != hipSuccess || (e = s.hbase.grow((size_t)nh)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(s.hist.get() + (nh - 1), 0, sizeof(uint32_t), stream)) != hipSuccess) return e;
+            sb.hist = s.hist.get();
             sb.nbricks = nbricks;
             g = G;
         } else {
@@ -1522,61 +1468,35 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         sb.hist = nullptr;  // the march kernels read none of it
         if (csort) {
             size_t tbh = 0;
-            if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, tbh, s.hist, s.hbase, (int)nh, stream)) != hipSuccess)
+            if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, tbh, s.hist.get(), s.hbase.get(), (int)nh, stream)) != hipSuccess)
                 return e;
-            if (tbh > s.temp_bytes) {
-                (void)hipFree(s.temp);
-                s.temp = nullptr;
-                s.temp_bytes = 0;
-                if ((e = hipMalloc(&s.temp, tbh)) != hipSuccess) return e;
-                s.temp_bytes = tbh;
-            }
-            if ((e = hipcub::DeviceScan::ExclusiveSum(s.temp, tbh, s.hist, s.hbase, (int)nh, stream)) != hipSuccess)
+            if ((e = s.temp.grow(tbh)) != hipSuccess) return e;
+            if ((e = hipcub::DeviceScan::ExclusiveSum(s.temp.get(), tbh, s.hist.get(), s.hbase.get(), (int)nh, stream)) != hipSuccess)
                 return e;
         }
         // exclusive scan of the brick counts (ns + 1 entries: the last gives the total); the
         // counting-sort forward needs none (its positions come from the histogram scan)
         size_t tb = 0;
         if (!csort || adj) {
-            if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sb.m, s.off, (int)(ns + 1), stream)) != hipSuccess)
+            if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sb.m, s.off.get(), (int)(ns + 1), stream)) != hipSuccess)
                 return e;
-            if (tb > s.temp_bytes) {
-                (void)hipFree(s.temp);
-                s.temp = nullptr;
-                s.temp_bytes = 0;
-                if ((e = hipMalloc(&s.temp, tb)) != hipSuccess) return e;
-                s.temp_bytes = tb;
-            }
-            if ((e = hipcub::DeviceScan::ExclusiveSum(s.temp, tb, sb.m, s.off, (int)(ns + 1), stream)) != hipSuccess)
+            if ((e = s.temp.grow(tb)) != hipSuccess) return e;
+            if ((e = hipcub::DeviceScan::ExclusiveSum(s.temp.get(), tb, sb.m, s.off.get(), (int)(ns + 1), stream)) != hipSuccess)
                 return e;
         }
         uint32_t total = 0;
-        if ((e = hipMemcpyAsync(&total, csort ? s.hbase + (nh - 1) : s.off + ns, sizeof(uint32_t),
+        if ((e = hipMemcpyAsync(&total, csort ? s.hbase.get() + (nh - 1) : s.off.get() + ns, sizeof(uint32_t),
                                 hipMemcpyDeviceToHost, stream)) != hipSuccess)
             return e;
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
-        if (cc && (int64_t)total > cc->cap_vals) {
-            (void)hipFree(cc->vals);
-            cc->vals = nullptr;
-            cc->cap_vals = 0;
-            const int64_t cap = (int64_t)total + total / 8;
-            if (room((size_t)cap * sizeof(uint32_t)) &&
-                hipMalloc((void**)&cc->vals, (size_t)cap * sizeof(uint32_t)) == hipSuccess)
-                cc->cap_vals = cap;
-            else
-                cc->vals = nullptr;
+        if (cc && (size_t)total > cc->vals.capacity()) {
+            (void)cc->vals.reset();
+            const size_t cap = (size_t)total + total / 8;
+            if (room(cap * sizeof(uint32_t))) (void)cc->vals.alloc(cap);
         }
-        if (cc && cc->cap_bricks < (int64_t)nbricks + 1) {
-            (void)hipFree(cc->bstart);
-            cc->bstart = nullptr;
-            cc->cap_bricks = 0;
-            if (hipMalloc((void**)&cc->bstart, ((size_t)nbricks + 1) * sizeof(uint32_t)) == hipSuccess)
-                cc->cap_bricks = (int64_t)nbricks + 1;
-            else
-                cc->bstart = nullptr;
-        }
+        if (cc) (void)cc->bstart.grow((size_t)nbricks + 1);
         // a chunk whose sorted slots find no room runs from the scratch arrays, uncached
-        const bool keep = cc && (total == 0 || (cc->vals && cc->bstart));
+        const bool keep = cc && (total == 0 || (cc->vals.get() && cc->bstart.get()));
         if (keep) cc->total = total;
         if (keep) cc->ws = csort;
         if (keep) ++s.st[2];
@@ -1588,46 +1508,34 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         // entry arrays: keys[0] (sort keys / the counting-sort adjoint's inv), vals[1] (sorted slots /
         // entries), part (adjoint partials); the radix sort's second buffers keys[1] / vals[0] only
         // on that path (cap_entries2)
+        const size_t cap = (size_t)total + total / 4;
         if ((int64_t)total > s.cap_entries) {
-            (void)hipFree(s.keys[0]);
-            (void)hipFree(s.vals[1]);
-            (void)hipFree(s.part);
-            s.keys[0] = s.vals[1] = nullptr;
-            s.part = nullptr;
             s.cap_entries = 0;
-            const int64_t cap = (int64_t)total + total / 4;
-            if ((e = hipMalloc((void**)&s.keys[0], cap * sizeof(uint32_t))) != hipSuccess ||
-                (e = hipMalloc((void**)&s.vals[1], cap * sizeof(uint32_t))) != hipSuccess ||
-                (e = hipMalloc((void**)&s.part, cap * sizeof(float))) != hipSuccess)
+            if ((e = s.keys[0].alloc(cap)) != hipSuccess || (e = s.vals[1].alloc(cap)) != hipSuccess ||
+                (e = s.part.alloc(cap)) != hipSuccess)
                 return e;
-            s.cap_entries = cap;
+            s.cap_entries = (int64_t)cap;
         }
         if (!csort && (int64_t)total > s.cap_entries2) {
-            (void)hipFree(s.keys[1]);
-            (void)hipFree(s.vals[0]);
-            s.keys[1] = s.vals[0] = nullptr;
             s.cap_entries2 = 0;
-            const int64_t cap = (int64_t)total + total / 4;
-            if ((e = hipMalloc((void**)&s.keys[1], cap * sizeof(uint32_t))) != hipSuccess ||
-                (e = hipMalloc((void**)&s.vals[0], cap * sizeof(uint32_t))) != hipSuccess)
-                return e;
-            s.cap_entries2 = cap;
+            if ((e = s.keys[1].alloc(cap)) != hipSuccess || (e = s.vals[0].alloc(cap)) != hipSuccess) return e;
+            s.cap_entries2 = (int64_t)cap;
         }
         if (csort) {
-            uint32_t* ent = keep ? cc->vals : s.vals[1];
-            uint32_t* bstart = keep ? cc->bstart : s.bstart;
-            uint32_t* inv = adj ? s.keys[0] : nullptr;
+            uint32_t* ent = keep ? cc->vals.get() : s.vals[1].get();
+            uint32_t* bstart = keep ? cc->bstart.get() : s.bstart.get();
+            uint32_t* inv = adj ? s.keys[0].get() : nullptr;
             hipLaunchKernelGGL(tvam_bin_bstart_kernel, dim3((unsigned)((nbricks + 256) / 256)), dim3(256), 0, stream,
-                               s.hbase, G, nbricks, bstart);
+                               s.hbase.get(), G, nbricks, bstart);
             hipLaunchKernelGGL(tvam_bin_fill2_kernel, dim3((unsigned)G), dim3(256), (size_t)nbricks * sizeof(uint32_t),
-                               stream, k, sb, ns, s.hbase, ent, adj ? s.off : nullptr, inv);
+                               stream, k, sb, ns, s.hbase.get(), ent, adj ? s.off.get() : nullptr, inv);
             if (adj) {
                 hipLaunchKernelGGL((tvam_bin_march_kernel<2, 1024, true>), dim3((unsigned)nbricks), dim3(1024), 0,
-                                   stream, k, sb, ent, bstart, nullptr, gin, 0u, nullptr, s.part);
+                                   stream, k, sb, ent, bstart, nullptr, gin, 0u, nullptr, s.part.get());
                 const int64_t npix = (p1 - p0) / spp;
                 g = std::min<int64_t>((npix + 3) / 4, 65536);  // a wave per pixel
-                hipLaunchKernelGGL(tvam_bin_reduce2_kernel, dim3((unsigned)g), dim3(256), 0, stream, sb, spp, s.off,
-                                   inv, s.part, idxmap, out);
+                hipLaunchKernelGGL(tvam_bin_reduce2_kernel, dim3((unsigned)g), dim3(256), 0, stream, sb, spp, s.off.get(),
+                                   inv, s.part.get(), idxmap, out);
             } else {
                 march_fwd(sb, ent, bstart, true);
             }
@@ -1636,62 +1544,50 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
             continue;
         }
         size_t tb2 = 0;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, s.keys[0], s.keys[1], s.vals[0], s.vals[1],
+        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, s.keys[0].get(), s.keys[1].get(), s.vals[0].get(), s.vals[1].get(),
                                                     (int)total, 0, bits, stream)) != hipSuccess)
             return e;
-        if (tb2 > s.temp_bytes) {
-            (void)hipFree(s.temp);
-            s.temp = nullptr;
-            s.temp_bytes = 0;
-            if ((e = hipMalloc(&s.temp, tb2)) != hipSuccess) return e;
-            s.temp_bytes = tb2;
-        }
+        if ((e = s.temp.grow(tb2)) != hipSuccess) return e;
         g = std::min<int64_t>((ns + TVAM_FILL_T - 1) / TVAM_FILL_T, 65536);
-        hipLaunchKernelGGL(tvam_bin_fill_kernel, dim3((unsigned)g), dim3(256), 0, stream, k, sb, s.off, ns, s.keys[0],
-                           s.vals[0], cbits);
-        uint32_t* vals_out = keep ? cc->vals : s.vals[1];
-        uint32_t* bstart = keep ? cc->bstart : s.bstart;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(s.temp, tb2, s.keys[0], s.keys[1], s.vals[0], vals_out,
+        hipLaunchKernelGGL(tvam_bin_fill_kernel, dim3((unsigned)g), dim3(256), 0, stream, k, sb, s.off.get(), ns, s.keys[0].get(),
+                           s.vals[0].get(), cbits);
+        uint32_t* vals_out = keep ? cc->vals.get() : s.vals[1].get();
+        uint32_t* bstart = keep ? cc->bstart.get() : s.bstart.get();
+        if ((e = hipcub::DeviceRadixSort::SortPairs(s.temp.get(), tb2, s.keys[0].get(), s.keys[1].get(), s.vals[0].get(), vals_out,
                                                     (int)total, 0, bits, stream)) != hipSuccess)
             return e;
         g = std::min<int64_t>(((int64_t)total + 256) / 256, 65536);
-        hipLaunchKernelGGL(tvam_bin_start_kernel, dim3((unsigned)g), dim3(256), 0, stream, s.keys[1], (int64_t)total,
+        hipLaunchKernelGGL(tvam_bin_start_kernel, dim3((unsigned)g), dim3(256), 0, stream, s.keys[1].get(), (int64_t)total,
                            nbricks, kmask, cbits, bstart);
         if (adj) {
             // partials at their sorted positions with their pixel (s.keys[1]: read by the start
             // kernel above, free now), sorted by pixel into keys[0] / vals[0] (free since the
             // sort), each pixel's run start in s.off (free since the fill), summed per pixel
-            uint32_t* ppix = s.keys[1];
+            uint32_t* ppix = s.keys[1].get();
             const uint32_t pslots = (uint32_t)spp * (uint32_t)slots;
             if (bin_nt == 1024)
                 hipLaunchKernelGGL((tvam_bin_march_kernel<2, 1024>), dim3((unsigned)nbricks), dim3(1024), 0, stream, k,
-                                   sb, s.vals[1], s.bstart, nullptr, gin, pslots, ppix, s.part);
+                                   sb, s.vals[1].get(), s.bstart.get(), nullptr, gin, pslots, ppix, s.part.get());
             else
                 hipLaunchKernelGGL((tvam_bin_march_kernel<2, 512>), dim3((unsigned)nbricks), dim3(512), 0, stream, k,
-                                   sb, s.vals[1], s.bstart, nullptr, gin, pslots, ppix, s.part);
+                                   sb, s.vals[1].get(), s.bstart.get(), nullptr, gin, pslots, ppix, s.part.get());
             const int64_t npix = (p1 - p0) / spp;
             int pbits = 1;
             while (((int64_t)1 << pbits) < npix) ++pbits;
-            float* psort = reinterpret_cast<float*>(s.vals[0]);
+            float* psort = reinterpret_cast<float*>(s.vals[0].get());
             size_t tb3 = 0;
-            if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb3, ppix, s.keys[0], s.part, psort, (int)total, 0,
+            if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb3, ppix, s.keys[0].get(), s.part.get(), psort, (int)total, 0,
                                                         pbits, stream)) != hipSuccess)
                 return e;
-            if (tb3 > s.temp_bytes) {
-                (void)hipFree(s.temp);
-                s.temp = nullptr;
-                s.temp_bytes = 0;
-                if ((e = hipMalloc(&s.temp, tb3)) != hipSuccess) return e;
-                s.temp_bytes = tb3;
-            }
-            if ((e = hipcub::DeviceRadixSort::SortPairs(s.temp, tb3, ppix, s.keys[0], s.part, psort, (int)total, 0,
+            if ((e = s.temp.grow(tb3)) != hipSuccess) return e;
+            if ((e = hipcub::DeviceRadixSort::SortPairs(s.temp.get(), tb3, ppix, s.keys[0].get(), s.part.get(), psort, (int)total, 0,
                                                         pbits, stream)) != hipSuccess)
                 return e;
             g = std::min<int64_t>(((int64_t)total + 256) / 256, 65536);
-            hipLaunchKernelGGL(tvam_bin_start_kernel, dim3((unsigned)g), dim3(256), 0, stream, s.keys[0],
-                               (int64_t)total, (int)npix, 0xffffffffu, 0, s.off);
+            hipLaunchKernelGGL(tvam_bin_start_kernel, dim3((unsigned)g), dim3(256), 0, stream, s.keys[0].get(),
+                               (int64_t)total, (int)npix, 0xffffffffu, 0, s.off.get());
             g = std::min<int64_t>((npix + 3) / 4, 65536);  // a wave per pixel
-            hipLaunchKernelGGL(tvam_bin_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, sb, spp, s.off, psort,
+            hipLaunchKernelGGL(tvam_bin_reduce_kernel, dim3((unsigned)g), dim3(256), 0, stream, sb, spp, s.off.get(), psort,
                                idxmap, out);
         } else {
             march_fwd(sb, vals_out, bstart, false);
@@ -1700,8 +1596,8 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         if (keep) cc->valid = true;
     }
     // the count check, read by a later call (above) or tvam_plan_bin_stats, without a sync here
-    if (s.sb.bad && s.st[0] > 0 && !s.bad_pending) {
-        if ((e = hipMemcpyAsync(s.bad_host, s.sb.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+    if (s.bad.get() && s.st[0] > 0 && !s.bad_pending) {
+        if ((e = hipMemcpyAsync(s.bad_host, s.bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
             (e = hipEventRecord(s.bad_ev, stream)) != hipSuccess)
             return e;
         s.bad_pending = true;

@@ -17,7 +17,7 @@
 // tests/test_gpu_vec_kernels.py pins the dots layout, the fp64 accumulation and that determinism.
 // The update passes of the first-order optimisers (SGD, Adam; the config's 'optimizer' entry) are
 // at the end of the file: tvam_optim_kernel.
-#include "tvam_internal.h"
+#include "tvam_plan.h"
 
 #define TVAM_VB 256       // threads per block
 #define TVAM_VGRID_MAX 2048  // most blocks of the reduction kernels (work[] holds grid * ndots doubles)
@@ -260,10 +260,11 @@ static hipError_t dispatch_hist(int h, uint64_t n, const float* p, const float* 
     }
 }
 
-hipError_t tvam_launch_lbfgs_history(uint64_t n, const float* p, const float* p_old, const float* g,
-                                     const float* g_old, int h, const float* const* S, const float* const* Y,
-                                     float* s_new, float* y_new, double* work, double* dots, hipStream_t stream,
-                                     uint64_t nseg, uint64_t seg_len, uint64_t seg_stride, uint64_t seg_off) {
+static hipError_t tvam_launch_lbfgs_history(uint64_t n, const float* p, const float* p_old, const float* g,
+                                            const float* g_old, int h, const float* const* S, const float* const* Y,
+                                            float* s_new, float* y_new, double* work, double* dots, hipStream_t stream,
+                                            uint64_t nseg = 0, uint64_t seg_len = 0, uint64_t seg_stride = 0,
+                                            uint64_t seg_off = 0) {
     VecPtrs hv{};
     for (int j = 0; j < h; ++j) {
         hv.s[j] = S[j];
@@ -340,7 +341,7 @@ __global__ __launch_bounds__(TVAM_VB) void tvam_lbfgs_dir_kernel(uint64_t n, con
     }
 }
 
-hipError_t tvam_launch_lbfgs_direction(uint64_t n, const float* g, int h, const float* const* S,
+static hipError_t tvam_launch_lbfgs_direction(uint64_t n, const float* g, int h, const float* const* S,
                                        const float* const* Y, float cg, const float* cs, const float* cy, float* d,
                                        hipStream_t stream) {
     VecPtrs hv{};
@@ -428,7 +429,7 @@ __global__ void tvam_lbfgs_coef_kernel(int H, int is_new, int first, LbfgsOrder 
     gdz[0] = r + rs + ry;
 }
 
-hipError_t tvam_launch_lbfgs_coef(int h, int is_new, int first, const int* order, const double* dots, double* gram,
+static hipError_t tvam_launch_lbfgs_coef(int h, int is_new, int first, const int* order, const double* dots, double* gram,
                                   float* coef, double* gdz, hipStream_t stream) {
     LbfgsOrder o{};
     for (int j = 0; j < h; ++j) o.slot[j] = order[j];
@@ -436,9 +437,10 @@ hipError_t tvam_launch_lbfgs_coef(int h, int is_new, int first, const int* order
     return hipGetLastError();
 }
 
-hipError_t tvam_launch_lbfgs_direction_dev(uint64_t n, const float* g, int h, const float* const* S,
-                                           const float* const* Y, const float* coef, float* d, hipStream_t stream,
-                                           uint64_t nseg, uint64_t seg_len, uint64_t seg_stride, uint64_t seg_off) {
+static hipError_t tvam_launch_lbfgs_direction_dev(uint64_t n, const float* g, int h, const float* const* S,
+                                                  const float* const* Y, const float* coef, float* d,
+                                                  hipStream_t stream, uint64_t nseg = 0, uint64_t seg_len = 0,
+                                                  uint64_t seg_stride = 0, uint64_t seg_off = 0) {
     VecPtrs hv{};
     for (int j = 0; j < h; ++j) {
         hv.s[j] = S[j];
@@ -501,8 +503,9 @@ __global__ __launch_bounds__(TVAM_VB) void tvam_axpy_clamp_kernel(uint64_t n, co
     }
 }
 
-hipError_t tvam_launch_axpy_clamp(uint64_t n, const float* p, float alpha, const float* d, float lo, float* out,
-                                  hipStream_t stream, const float* alpha_dev, float* s_out) {
+static hipError_t tvam_launch_axpy_clamp(uint64_t n, const float* p, float alpha, const float* d, float lo, float* out,
+                                         hipStream_t stream, const float* alpha_dev = nullptr,
+                                         float* s_out = nullptr) {
     hipLaunchKernelGGL(tvam_axpy_clamp_kernel, dim3(2048), dim3(TVAM_VB), 0, stream, n, p, alpha, d, lo, out,
                        alpha_dev, s_out);
     return hipGetLastError();
@@ -545,7 +548,7 @@ __global__ void tvam_armijo_kernel(int nprobe, double a0, const double* __restri
     }
 }
 
-hipError_t tvam_launch_armijo(int nprobe, double a0, const double* probes, const double* loss_dev, double loss_host,
+static hipError_t tvam_launch_armijo(int nprobe, double a0, const double* probes, const double* loss_dev, double loss_host,
                               double loss_div, const double* gdz, double c1, float* alpha, double* report,
                               hipStream_t stream) {
     hipLaunchKernelGGL(tvam_armijo_kernel, dim3(1), dim3(64), 0, stream, nprobe, a0, probes, loss_dev, loss_host,
@@ -692,14 +695,14 @@ static hipError_t launch_optim(bool mask, OptimArgs q, double* S_out, hipStream_
     return hipGetLastError();
 }
 
-hipError_t tvam_launch_sgd_step(uint64_t n, float* p, const float* g, float* s, float lr, float mu, bool mask,
+static hipError_t tvam_launch_sgd_step(uint64_t n, float* p, const float* g, float* s, float lr, float mu, bool mask,
                                 float lo, hipStream_t stream) {
     OptimArgs q{};
     q.n = n, q.p = p, q.g = g, q.a = s, q.lr = lr, q.k1 = mu, q.lo = lo;
     return s ? launch_optim<TVAM_OPT_SGDM>(mask, q, nullptr, stream) : launch_optim<TVAM_OPT_SGD>(mask, q, nullptr, stream);
 }
 
-hipError_t tvam_launch_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1,
+static hipError_t tvam_launch_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1,
                                  float c1, float b2, float c2, float eps, bool mask, float lo, hipStream_t stream) {
     OptimArgs q{};
     q.n = n, q.p = p, q.g = g, q.a = m, q.b = v, q.lr = lr_t, q.k1 = b1, q.c1 = c1, q.k2 = b2, q.c2 = c2;
@@ -707,18 +710,183 @@ hipError_t tvam_launch_adam_step(uint64_t n, float* p, const float* g, float* m,
     return launch_optim<TVAM_OPT_ADAM>(mask, q, nullptr, stream);
 }
 
-hipError_t tvam_launch_adam_moments(uint64_t n, const float* g, float* m, float* v, float b1, float c1, float b2,
+static hipError_t tvam_launch_adam_moments(uint64_t n, const float* g, float* m, float* v, float b1, float c1, float b2,
                                     float c2, bool mask, double* work, double* S, hipStream_t stream) {
     OptimArgs q{};
     q.n = n, q.g = g, q.a = m, q.b = v, q.k1 = b1, q.c1 = c1, q.k2 = b2, q.c2 = c2, q.work = work;
     return launch_optim<TVAM_OPT_MOMENTS>(mask, q, S, stream);
 }
 
-hipError_t tvam_launch_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
+static hipError_t tvam_launch_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
                                   const double* count, float lr_t, float eps, bool mask, float lo,
                                   hipStream_t stream) {
     OptimArgs q{};
     q.n = n, q.p = p, q.g = mask ? g : nullptr, q.a = const_cast<float*>(m), q.S = S, q.count = count;
     q.lr = lr_t, q.eps = eps, q.lo = lo;
     return launch_optim<TVAM_OPT_APPLY>(mask, q, nullptr, stream);
+}
+
+// The extern "C" boundary of these kernels (include/tvam.h).
+static bool aligned16(const void* q) { return ((uintptr_t)q & 15u) == 0; }
+
+extern "C" int tvam_lbfgs_history(uint64_t n, const float* p, const float* p_old, const float* g, const float* g_old,
+                                  int32_t h, const float* const* S, const float* const* Y, float* s_new,
+                                  float* y_new, double* work, double* dots, void* stream) {
+    if (!g || !work || !dots || (h > 0 && (!S || !Y))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (h < 0 || h > 7) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history: 0 <= h <= 7 retained pairs");
+    if (p_old && (!p || !g_old || !s_new || !y_new)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    // p_old NULL with g_old given: a new pair whose s_new already holds p - p_old (read, not written)
+    const bool spre = !p_old && g_old;
+    if (spre && (!s_new || !y_new)) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history: precomputed s_new needs s_new, y_new");
+    bool ok = aligned16(g) && (!p_old || (aligned16(p) && aligned16(p_old) && aligned16(g_old) &&
+                                          aligned16(s_new) && aligned16(y_new))) &&
+              (!spre || (aligned16(g_old) && aligned16(s_new) && aligned16(y_new)));
+    for (int j = 0; j < h; ++j) ok = ok && S[j] && Y[j] && aligned16(S[j]) && aligned16(Y[j]);
+    if (!ok) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history: vectors must be 16-byte aligned");
+    hipError_t e = tvam_launch_lbfgs_history(n, p, p_old, g, g_old, h, S, Y, s_new, y_new, work, dots,
+                                             (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "lbfgs history launch");
+}
+
+extern "C" int tvam_lbfgs_history_rows(uint64_t nseg, uint64_t seg_len, uint64_t seg_stride, uint64_t seg_off,
+                                       const float* p, const float* p_old, const float* g, const float* g_old,
+                                       int32_t h, const float* const* S, const float* const* Y, float* s_new,
+                                       float* y_new, double* work, double* dots, void* stream) {
+    if (!g || !work || !dots || (h > 0 && (!S || !Y))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (h < 0 || h > 7) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history_rows: 0 <= h <= 7 retained pairs");
+    if (p_old && (!p || !g_old || !s_new || !y_new)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (!p_old && g_old) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history_rows: g_old without p_old");
+    if (nseg == 0 || seg_len == 0 || seg_len % 4 || seg_stride % 4 || seg_off % 4 || seg_len > seg_stride ||
+        seg_len / 4 > 0xffffffffull)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history_rows: segments of a multiple of 4 entries, 4-aligned");
+    bool ok = aligned16(g) && (!p_old || (aligned16(p) && aligned16(p_old) && aligned16(g_old) &&
+                                          aligned16(s_new) && aligned16(y_new)));
+    for (int j = 0; j < h; ++j) ok = ok && S[j] && Y[j] && aligned16(S[j]) && aligned16(Y[j]);
+    if (!ok) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_history_rows: vectors must be 16-byte aligned");
+    hipError_t e = tvam_launch_lbfgs_history(0, p, p_old, g, g_old, h, S, Y, s_new, y_new, work, dots,
+                                             (hipStream_t)stream, nseg, seg_len, seg_stride, seg_off);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "lbfgs history launch");
+}
+
+extern "C" int tvam_lbfgs_direction(uint64_t n, const float* g, int32_t h, const float* const* S,
+                                    const float* const* Y, float cg, const float* cs, const float* cy, float* d,
+                                    void* stream) {
+    if (!g || !d || (h > 0 && (!S || !Y || !cs || !cy))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (h < 0 || h > 8) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction: 0 <= h <= 8 pairs");
+    bool ok = aligned16(g) && aligned16(d);
+    for (int j = 0; j < h; ++j) ok = ok && S[j] && Y[j] && aligned16(S[j]) && aligned16(Y[j]);
+    if (!ok) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction: vectors must be 16-byte aligned");
+    hipError_t e = tvam_launch_lbfgs_direction(n, g, h, S, Y, cg, cs, cy, d, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "lbfgs direction launch");
+}
+
+extern "C" int tvam_lbfgs_coef(int32_t h, int32_t is_new, int32_t first, const int32_t* order, const double* dots,
+                               double* gram, float* coef, double* gdz, void* stream) {
+    if (h < 0 || h > 8) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_coef: 0 <= h <= 8 pairs");
+    if (!dots || !gram || !coef || !gdz || (h > 0 && !order)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (is_new && h == 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_coef: a new pair needs h >= 1");
+    for (int j = 0; j < h; ++j)
+        if (order[j] < 0 || order[j] >= 8) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_coef: ring slots are 0..7");
+    hipError_t e = tvam_launch_lbfgs_coef(h, is_new ? 1 : 0, first ? 1 : 0, order, dots, gram, coef, gdz,
+                                          (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "lbfgs coefficient launch");
+}
+
+extern "C" int tvam_lbfgs_direction_dev(uint64_t n, const float* g, int32_t h, const float* const* S,
+                                        const float* const* Y, const float* coef, float* d, void* stream) {
+    if (!g || !d || !coef || (h > 0 && (!S || !Y))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (h < 0 || h > 8) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction_dev: 0 <= h <= 8 pairs");
+    bool ok = aligned16(g) && aligned16(d);
+    for (int j = 0; j < h; ++j) ok = ok && S[j] && Y[j] && aligned16(S[j]) && aligned16(Y[j]);
+    if (!ok) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction_dev: vectors must be 16-byte aligned");
+    hipError_t e = tvam_launch_lbfgs_direction_dev(n, g, h, S, Y, coef, d, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "lbfgs direction launch");
+}
+
+extern "C" int tvam_lbfgs_direction_rows(uint64_t nseg, uint64_t seg_len, uint64_t seg_stride, uint64_t seg_off,
+                                         const float* g, int32_t h, const float* const* S, const float* const* Y,
+                                         const float* coef, float* d, void* stream) {
+    if (!g || !d || !coef || (h > 0 && (!S || !Y))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (h < 0 || h > 8) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction_rows: 0 <= h <= 8 pairs");
+    if (nseg == 0 || seg_len == 0 || seg_len % 4 || seg_stride % 4 || seg_off % 4 || seg_len > seg_stride ||
+        seg_len / 4 > 0xffffffffull)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction_rows: segments of a multiple of 4 entries, 4-aligned");
+    bool ok = aligned16(g) && aligned16(d);
+    for (int j = 0; j < h; ++j) ok = ok && S[j] && Y[j] && aligned16(S[j]) && aligned16(Y[j]);
+    if (!ok) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_direction_rows: vectors must be 16-byte aligned");
+    hipError_t e = tvam_launch_lbfgs_direction_dev(0, g, h, S, Y, coef, d, (hipStream_t)stream, nseg, seg_len,
+                                                   seg_stride, seg_off);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "lbfgs direction launch");
+}
+
+extern "C" int tvam_axpy_clamp(uint64_t n, const float* p, float alpha, const float* d, float lo, float* out,
+                               void* stream) {
+    if (!p || !d || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (!aligned16(p) || !aligned16(d) || !aligned16(out))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_axpy_clamp: vectors must be 16-byte aligned");
+    hipError_t e = tvam_launch_axpy_clamp(n, p, alpha, d, lo, out, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "axpy launch");
+}
+
+extern "C" int tvam_axpy_clamp_dev(uint64_t n, const float* p, const float* alpha, const float* d, float lo,
+                                   float* out, float* s_out, void* stream) {
+    if (!p || !alpha || !d || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (!aligned16(p) || !aligned16(d) || !aligned16(out) || (s_out && !aligned16(s_out)))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_axpy_clamp_dev: vectors must be 16-byte aligned");
+    if (s_out && (s_out == p || s_out == out || s_out == d))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_axpy_clamp_dev: s_out must not alias p, d or out");
+    hipError_t e = tvam_launch_axpy_clamp(n, p, 0.0f, d, lo, out, (hipStream_t)stream, alpha, s_out);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "axpy launch");
+}
+
+extern "C" int tvam_lbfgs_armijo(int32_t nprobe, double alpha0, const double* probes, const double* loss_dev,
+                                 double loss_host, double loss_div, const double* gdz, double c1, float* alpha,
+                                 double* report, void* stream) {
+    if (!probes || !gdz || !alpha) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (nprobe < 1 || nprobe > 64) return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_armijo: 1 <= nprobe <= 64");
+    if (!(alpha0 > 0.0) || !(loss_div > 0.0))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_lbfgs_armijo: alpha0 and loss_div must be positive");
+    hipError_t e = tvam_launch_armijo(nprobe, alpha0, probes, loss_dev, loss_host, loss_div, gdz, c1, alpha, report,
+                                      (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "armijo launch");
+}
+
+// First-order optimiser updates.  The hyper-parameters arrive as doubles and are rounded here:
+// lr, beta and epsilon to fp32, 1 - beta in double and then to fp32.
+extern "C" int tvam_sgd_step(uint64_t n, float* p, const float* g, float* s, double lr, double momentum, int32_t mask,
+                             float lo, void* stream) {
+    if (!p || !g) return tvam_fail(TVAM_ERR_INVALID, "tvam_sgd_step: null argument");
+    if (!s && momentum != 0.0) return tvam_fail(TVAM_ERR_INVALID, "tvam_sgd_step: momentum needs the state vector s");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_sgd_step(n, p, g, s, (float)lr, (float)momentum, mask != 0, lo, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "sgd step launch");
+}
+
+extern "C" int tvam_adam_step(uint64_t n, float* p, const float* g, float* m, float* v, double lr_t, double beta_1,
+                              double beta_2, double epsilon, int32_t mask, float lo, void* stream) {
+    if (!p || !g || !m || !v) return tvam_fail(TVAM_ERR_INVALID, "tvam_adam_step: null argument");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_adam_step(n, p, g, m, v, (float)lr_t, (float)beta_1, (float)(1.0 - beta_1),
+                                         (float)beta_2, (float)(1.0 - beta_2), (float)epsilon, mask != 0, lo,
+                                         (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "adam step launch");
+}
+
+extern "C" int tvam_adam_moments(uint64_t n, const float* g, float* m, float* v, double beta_1, double beta_2,
+                                 int32_t mask, double* work, double* S, void* stream) {
+    if (!g || !m || !v || !work || !S) return tvam_fail(TVAM_ERR_INVALID, "tvam_adam_moments: null argument");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_adam_moments(n, g, m, v, (float)beta_1, (float)(1.0 - beta_1), (float)beta_2,
+                                            (float)(1.0 - beta_2), mask != 0, work, S, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "adam moments launch");
+}
+
+extern "C" int tvam_adam_apply(uint64_t n, float* p, const float* g, const float* m, const double* S,
+                               const double* count, double lr_t, double epsilon, int32_t mask, float lo,
+                               void* stream) {
+    if (!p || !m || !S || !count || (mask && !g)) return tvam_fail(TVAM_ERR_INVALID, "tvam_adam_apply: null argument");
+    if (n == 0) return 0;
+    hipError_t e = tvam_launch_adam_apply(n, p, g, m, S, count, (float)lr_t, (float)epsilon, mask != 0, lo,
+                                          (hipStream_t)stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "adam apply launch");
 }

@@ -21,6 +21,11 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def device_bytes() -> int:
+    """Bytes of device memory libtvam.so owns in this process (tvam_device_bytes): 0 without plans."""
+    return int(_abi.load_library().tvam_device_bytes())
+
+
 def derive_seed_grad(seed: int) -> int:
     """Seed of the adjoint pass when none is given (decorrelated from the primal)."""
     v0, v1 = seed & 0xFFFFFFFF, 1

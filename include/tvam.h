@@ -537,6 +537,12 @@ const char* tvam_last_error(void);
 /* ABI version of the loaded library. */
 int tvam_abi_version(void);
 
+/* Bytes of device memory the library owns in this process, over all plans and devices: the plans'
+   tables, ray records, scratch and caches, and the temporaries of a running call.  0 before the
+   first plan and again after the last tvam_plan_destroy.  (Added to ABI v13: no struct or existing
+   signature changed.) */
+int64_t tvam_device_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

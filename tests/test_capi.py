@@ -105,3 +105,19 @@ def test_round4_vector_entry_points_validate_before_hip():
     for i, rc in enumerate(cases):
         assert rc in (_abi.TVAM_ERR_INVALID, _abi.TVAM_ERR_UNSUPPORTED), (i, rc)
     assert lib.tvam_last_error()
+
+
+def test_device_bytes_zero_without_a_plan():
+    """tvam_device_bytes() is 0 in a process that has created no plan (a fresh one: plans of other
+    tests may still live in this process), also after a creation that validation rejects."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(HEADER))
+    code = ("import ctypes, sys; sys.path.insert(0, sys.argv[1]); from drtvam_amd import _abi\n"
+            "lib = _abi.load_library(); n0 = lib.tvam_device_bytes()\n"
+            "d = _abi.default_desc(); plan = ctypes.c_void_p()\n"
+            "rc = lib.tvam_plan_create(ctypes.byref(d), 0, ctypes.byref(plan))  # vial_r = 0: invalid\n"
+            "print(n0, rc != 0, lib.tvam_device_bytes())")
+    r = subprocess.run([sys.executable, "-c", code, root], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.split() == ["0", "True", "0"], r.stdout

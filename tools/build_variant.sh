@@ -11,13 +11,14 @@ mkdir -p "$cache" "$here/_variants"
 flags=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
        -munsafe-fp-atomics -Wall -Wno-unused-function -I"$here/include")
 objs=()
-for src in tvam_plan tvam_kernels tvam_planar tvam_adjlist tvam_vec tvam_scatter tvam_radon; do
+for src in "$cs"/*.hip; do  # every translation unit (the glob sorts)
+  src="$(basename "$src" .hip)"
   if [ "$src" = "$vsrc" ]; then
     o="$cache/${src}_$name.o"
     /opt/rocm/bin/hipcc "${flags[@]}" $vflags -c "$cs/$src.hip" -o "$o"
   else
     o="$cache/$src.o"
-    if [ ! -f "$o" ] || [ "$cs/$src.hip" -nt "$o" ] || [ "$cs/tvam_internal.h" -nt "$o" ]; then
+    if [ ! -f "$o" ] || [ "$cs/$src.hip" -nt "$o" ] || [ -n "$(find "$cs" -name '*.h' -newer "$o")" ]; then
       /opt/rocm/bin/hipcc "${flags[@]}" -c "$cs/$src.hip" -o "$o"
     fi
   fi
