@@ -163,6 +163,7 @@ EXPORTS = {
                                        ctypes.c_int32, ctypes.c_float, _P]),
     "tvam_row_slices": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P]),
     "tvam_plan_path": (ctypes.c_int, [_P]),
+    "tvam_plan_fwd_variant": (ctypes.c_int, [_P, _P]),
     "tvam_adjoint_slices": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_int32, _P, _P]),
     "tvam_plan_adj_chunk": (ctypes.c_int, [_P]),

@@ -614,6 +614,24 @@ extern "C" int tvam_plan_path(const tvam_plan* p) {
     return p ? (p->planar ? 1 : 0) | (p->planar_fwd ? 2 : 0) | (p->cone ? 4 : 0) : 0;
 }
 
+extern "C" int tvam_plan_fwd_variant(const tvam_plan* p, int32_t* v) {
+    if (!p || !v) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (!p->planar_fwd)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_fwd_variant: the voxel-driven forward does not serve this plan");
+    TvamFwdVariant fv;
+    if (!tvam_planar_fwd_variant(p->pl, p->planar_fz, fv))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_fwd_variant: no instantiated forward kernel serves the plan's tables");
+    v[0] = fv.z;
+    v[1] = fv.nc;
+    v[2] = p->pl.fwd_nc;
+    v[3] = p->pl.ncmax;
+    v[4] = fv.ab;
+    v[5] = fv.pf;
+    v[6] = (fv.bin ? 1 : 0) | (fv.dma ? 2 : 0) | (fv.multi ? 4 : 0) | (fv.refr ? 8 : 0) | (fv.sconst ? 16 : 0);
+    v[7] = p->pl.fwd_parts > 1 ? p->pl.fwd_parts : 1;
+    return 0;
+}
+
 extern "C" int tvam_plan_stats(tvam_plan* p, uint64_t* fallback_tiles) {
     if (!p || !fallback_tiles) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     unsigned long long h = 0;

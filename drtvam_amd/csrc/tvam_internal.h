@@ -144,6 +144,15 @@ size_t tvam_planar_fwd_lds(const TvamPlanar& pl, int Z);
 bool tvam_planar_fwd_fits(const TvamPlanar& pl, int Z);
 bool tvam_planar_fwd_dma_ok(const TvamPlanar& pl, int Z);
 bool tvam_planar_fwd_dma_window(const TvamPlanar& pl, int Z);
+// The instantiation of the voxel-driven forward kernel that serves a plan: its template arguments
+// (z .. dmap) and the staging the kernel derives from them (dma: LDS-DMA, sconst: per-angle
+// constants in SGPRs).
+struct TvamFwdVariant {
+    int z, nc, pf, ab;
+    bool multi, bin, refr, dmap;
+    bool dma, sconst;
+};
+bool tvam_planar_fwd_variant(const TvamPlanar& pl, int Z, TvamFwdVariant& v);
 hipError_t tvam_launch_fwd_planar(const TvamConsts& k, const TvamPlanar& pl, int Z, const float* pat, float* dose,
                                   hipStream_t stream);
 size_t tvam_planar_adj_lds(const TvamPlanar& pl, const TvamTiles& t, int Z);

@@ -117,6 +117,14 @@ static int validate(const tvam_desc& d) {
     if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CYLINDRICAL &&
         d.vial_type != TVAM_VIAL_SQUARE)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'index_matched', 'cylindrical' and 'square' containers are implemented on the GPU path");
+    // transmission_only = False lets the reference sample reflection as well as refraction at every
+    // dielectric interface after the first (volume.py:235-243, radon.py:87-95); the kernels only
+    // refract.  An index-matched vial has no such interface.
+    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !d.transmission_only)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED,
+                         std::string("transmission_only = 0 behind a ") +
+                             (d.vial_type == TVAM_VIAL_SQUARE ? "'square'" : "'cylindrical'") +
+                             " vial (reflected paths at the glass interfaces) is not implemented on the GPU path");
     if (d.n_occluder_tris < 0 || (d.n_occluder_tris > 0 && !d.occluder_tris))
         return tvam_fail(TVAM_ERR_INVALID, "occluder_tris is null");
     if (d.film_channels != 1 && d.film_channels != 2) return tvam_fail(TVAM_ERR_INVALID, "film_channels must be 1 or 2");
@@ -453,6 +461,7 @@ static int planar_setup(tvam_plan* p, const std::vector<float2>& cs) {
     TvamDevBuf<float4> chord;
     const int rc = planar_tables(p, cs, chord);
     p->pl.chord = nullptr;
+    if (!p->planar) p->planar_fwd = false;  // the planar path was given up after the forward's tables were chosen
     return rc;
 }
 

@@ -938,74 +938,100 @@ hipError_t tvam_launch_refr_model(const TvamConsts& k, const TvamPlanar& pl, con
 // launch itself (hipExtLaunchKernelGGL: no event packets between the kernels); null: untimed
 static thread_local hipEvent_t g_fwd_ev[2] = {nullptr, nullptr};
 
-template <int Z, int NC>
-static void launch_fwd(dim3 grid, size_t lds, hipStream_t stream, const TvamConsts& k, const TvamPlanar& pl,
-                       const float* pat, float* dose) {
-    if (pl.fwd_bin && pl.fwd_dma) {  // binned slabs staged by LDS-DMA
-        if (pl.fwd_refr)
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, 2, false, 1, 2, true, true, true>), grid, dim3(TVAM_PB), lds,
-                               stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-        else if (pl.fwd_ab == 1)
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 1, 1, true, false, true>), grid, dim3(TVAM_PB), lds,
-                               stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-        else
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 1, 2, true, false, true>), grid, dim3(TVAM_PB), lds,
-                               stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-        return;
-    }
-    if (pl.fwd_refr) {  // refracted chords: binned staging, 2 angles per barrier, candidates per (tile, angle)
-        if (pl.fwd_pf == 1)
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, 2, false, 1, 2, true, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0,
-                               k, pl, pat, dose);
-        else
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, 2, false, 2, 2, true, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0,
-                               k, pl, pat, dose);
-        return;
-    }
-    if constexpr (Z > 32) {  // deep slabs (thin-slab shards, 400-slice films in 10 chunks): binned staging only
-        if (pl.fwd_pf == 1)
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 1, 2, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl,
-                               pat, dose);
-        else
-            hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 2, 2, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl,
-                               pat, dose);
-        return;
-    }
-    if (pl.fwd_bin && pl.fwd_pf == 1 && pl.fwd_ab == 1)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 1, 1, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (pl.fwd_bin && pl.fwd_pf == 1)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 1, 2, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (pl.fwd_bin)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 2, 2, true>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (pl.fwd_multi)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, true, 4, 1>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (pl.fwd_pf == 2)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 2, 1>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (NC == 2 && pl.fwd_ab == 4)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 4, 4>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (NC == 2 && pl.fwd_ab == 3)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 4, 3>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
-    else if (NC == 2 && pl.fwd_ab == 2)
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 4, 2>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
+// The instantiation of tvam_fwd_planar_kernel that serves plan tables `pl` at depth Z: the one
+// definition of the choice, read by the launcher below and by tvam_plan_fwd_variant.  False when
+// no instantiated kernel serves them.
+bool tvam_planar_fwd_variant(const TvamPlanar& pl, int Z, TvamFwdVariant& v) {
+    v = TvamFwdVariant{};
+    if (Z != 8 && Z != 16 && Z != 24 && Z != 28 && Z != 32 && Z != 40 && Z != 48 && Z != 52 && Z != 60) return false;
+    const bool bin = pl.fwd_bin != nullptr;
+    if ((Z > 32 || pl.fwd_refr) && !bin) return false;  // deep slabs and refracted chords: binned staging only
+    v.z = Z;
+    v.refr = pl.fwd_refr != 0;
+    if (v.refr)
+        v.nc = 2;  // candidates per (tile, angle) at run time; two run straight-line
+    else if (pl.fwd_nc >= 1 && pl.fwd_nc <= 4)
+        v.nc = pl.fwd_nc < 2 ? 2 : pl.fwd_nc;
     else
-        hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, false, 4, 1>), grid, dim3(TVAM_PB), lds, stream, g_fwd_ev[0], g_fwd_ev[1], 0, k, pl, pat, dose);
+        return false;
+    v.bin = bin;
+    if (bin && pl.fwd_dma) {  // binned slabs staged by LDS-DMA
+        v.dmap = true;
+        v.pf = 1;
+        v.ab = !v.refr && pl.fwd_ab == 1 ? 1 : 2;
+    } else if (v.refr || Z > 32) {  // register-staged binned slabs, 2 angles per barrier
+        v.pf = pl.fwd_pf == 1 ? 1 : 2;
+        v.ab = 2;
+    } else if (bin) {
+        v.pf = pl.fwd_pf == 1 ? 1 : 2;
+        v.ab = v.pf == 1 && pl.fwd_ab == 1 ? 1 : 2;
+    } else if (pl.fwd_multi) {  // staged from the [row][col] patterns, some slice summing several rows
+        v.multi = true;
+        v.pf = 4;
+        v.ab = 1;
+    } else if (pl.fwd_pf == 2) {
+        v.pf = 2;
+        v.ab = 1;
+    } else {
+        v.pf = 4;
+        v.ab = v.nc == 2 && pl.fwd_ab >= 2 && pl.fwd_ab <= 4 ? pl.fwd_ab : 1;
+    }
+    // as the kernel derives them from its template arguments
+    v.dma = v.bin && v.dmap && v.ab <= 2;
+    v.sconst = v.dma && !v.refr && v.ab == 2;
+    return true;
+}
+
+struct FwdLaunch {
+    dim3 grid;
+    size_t lds;
+    hipStream_t stream;
+    const TvamConsts& k;
+    const TvamPlanar& pl;
+    const float* pat;
+    float* dose;
+};
+
+// Launches this instantiation when it is the variant's (its template arguments are compared with
+// the variant, so the variant reported is the kernel launched).
+template <int Z, int NC, bool MULTI, int PF, int AB, bool BIN = false, bool REFR = false, bool DMAP = false>
+static bool launch_fwd_if(const TvamFwdVariant& v, const FwdLaunch& a) {
+    if (v.z != Z || v.nc != NC || v.multi != MULTI || v.pf != PF || v.ab != AB || v.bin != BIN || v.refr != REFR ||
+        v.dmap != DMAP)
+        return false;
+    hipExtLaunchKernelGGL((tvam_fwd_planar_kernel<Z, NC, MULTI, PF, AB, BIN, REFR, DMAP>), a.grid, dim3(TVAM_PB), a.lds,
+                          a.stream, g_fwd_ev[0], g_fwd_ev[1], 0, a.k, a.pl, a.pat, a.dose);
+    return true;
+}
+
+// the instantiated kernels of depth Z and NC candidates
+template <int Z, int NC>
+static bool launch_fwd(const TvamFwdVariant& v, const FwdLaunch& a) {
+    if constexpr (NC == 2) {  // refracted chords
+        if (launch_fwd_if<Z, 2, false, 1, 2, true, true, true>(v, a) || launch_fwd_if<Z, 2, false, 1, 2, true, true>(v, a) ||
+            launch_fwd_if<Z, 2, false, 2, 2, true, true>(v, a))
+            return true;
+    }
+    // binned slabs: LDS-DMA, then register staging
+    if (launch_fwd_if<Z, NC, false, 1, 1, true, false, true>(v, a) || launch_fwd_if<Z, NC, false, 1, 2, true, false, true>(v, a) ||
+        launch_fwd_if<Z, NC, false, 1, 2, true>(v, a) || launch_fwd_if<Z, NC, false, 2, 2, true>(v, a))
+        return true;
+    if constexpr (Z <= 32) {  // (deep slabs: binned staging only)
+        if (launch_fwd_if<Z, NC, false, 1, 1, true>(v, a) || launch_fwd_if<Z, NC, true, 4, 1>(v, a) ||
+            launch_fwd_if<Z, NC, false, 2, 1>(v, a) || launch_fwd_if<Z, NC, false, 4, 1>(v, a))
+            return true;
+        if constexpr (NC == 2) {
+            if (launch_fwd_if<Z, 2, false, 4, 4>(v, a) || launch_fwd_if<Z, 2, false, 4, 3>(v, a) ||
+                launch_fwd_if<Z, 2, false, 4, 2>(v, a))
+                return true;
+        }
+    }
+    return false;
 }
 
 template <int Z>
-static hipError_t launch_fwd_z(dim3 grid, size_t lds, hipStream_t stream, const TvamConsts& k, const TvamPlanar& pl,
-                               const float* pat, float* dose) {
-    if (pl.fwd_refr) {
-        launch_fwd<Z, 2>(grid, lds, stream, k, pl, pat, dose);
-        return hipGetLastError();
-    }
-    switch (pl.fwd_nc) {
-        case 1:
-        case 2: launch_fwd<Z, 2>(grid, lds, stream, k, pl, pat, dose); break;
-        case 3: launch_fwd<Z, 3>(grid, lds, stream, k, pl, pat, dose); break;
-        case 4: launch_fwd<Z, 4>(grid, lds, stream, k, pl, pat, dose); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+static bool launch_fwd_z(const TvamFwdVariant& v, const FwdLaunch& a) {
+    return launch_fwd<Z, 2>(v, a) || launch_fwd<Z, 3>(v, a) || launch_fwd<Z, 4>(v, a);
 }
 
 static hipError_t tvam_launch_fwd_planar_z(dim3 grid, size_t lds, hipStream_t stream, const TvamConsts& k,
@@ -1050,18 +1076,13 @@ hipError_t tvam_launch_fwd_planar(const TvamConsts& k, const TvamPlanar& pl, int
 
 static hipError_t tvam_launch_fwd_planar_z(dim3 grid, size_t lds, hipStream_t stream, const TvamConsts& k,
                                            const TvamPlanar& pl, int Z, const float* pat, float* dose) {
-    switch (Z) {
-        case 8: return launch_fwd_z<8>(grid, lds, stream, k, pl, pat, dose);
-        case 16: return launch_fwd_z<16>(grid, lds, stream, k, pl, pat, dose);
-        case 24: return launch_fwd_z<24>(grid, lds, stream, k, pl, pat, dose);
-        case 28: return launch_fwd_z<28>(grid, lds, stream, k, pl, pat, dose);
-        case 32: return launch_fwd_z<32>(grid, lds, stream, k, pl, pat, dose);
-        case 40: return pl.fwd_bin ? launch_fwd_z<40>(grid, lds, stream, k, pl, pat, dose) : hipErrorInvalidValue;
-        case 48: return pl.fwd_bin ? launch_fwd_z<48>(grid, lds, stream, k, pl, pat, dose) : hipErrorInvalidValue;
-        case 52: return pl.fwd_bin ? launch_fwd_z<52>(grid, lds, stream, k, pl, pat, dose) : hipErrorInvalidValue;
-        case 60: return pl.fwd_bin ? launch_fwd_z<60>(grid, lds, stream, k, pl, pat, dose) : hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
+    TvamFwdVariant v;
+    if (!tvam_planar_fwd_variant(pl, Z, v)) return hipErrorInvalidValue;
+    const FwdLaunch a{grid, lds, stream, k, pl, pat, dose};
+    const bool ok = launch_fwd_z<8>(v, a) || launch_fwd_z<16>(v, a) || launch_fwd_z<24>(v, a) || launch_fwd_z<28>(v, a) ||
+                    launch_fwd_z<32>(v, a) || launch_fwd_z<40>(v, a) || launch_fwd_z<48>(v, a) || launch_fwd_z<52>(v, a) ||
+                    launch_fwd_z<60>(v, a);
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------

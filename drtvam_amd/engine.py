@@ -252,6 +252,20 @@ class Projection:
         """True when the voxel-driven planar forward serves this plan (straight rays)."""
         return bool(self.lib.tvam_plan_path(self._plan) & 2)
 
+    def fwd_variant(self) -> dict:
+        """The voxel-driven forward kernel this plan launches (tvam_plan_fwd_variant): Z slices per
+        workgroup, NC candidate columns instantiated, the plan's candidate count nc, the staged window
+        ncmax, AB angles per barrier, PF staged values per thread, the flags BIN / DMA / MULTI / REFR /
+        SCONST and the angle parts.  ValueError when the voxel-driven forward does not serve the plan."""
+        import numpy as np
+        v = np.zeros(8, dtype=np.int32)
+        _abi.check(self.lib.tvam_plan_fwd_variant(self._plan, v.ctypes.data))
+        out = dict(zip(("Z", "NC", "nc", "ncmax", "AB", "PF"), (int(x) for x in v[:6])))
+        for bit, name in enumerate(("BIN", "DMA", "MULTI", "REFR", "SCONST")):
+            out[name] = bool(int(v[6]) >> bit & 1)
+        out["parts"] = int(v[7])
+        return out
+
     def fallback_tiles(self) -> int:
         """Workgroups of the last forward that used float LDS atomics (needs FLAG_FWD_STATS)."""
         v = ctypes.c_uint64(0)

@@ -342,6 +342,17 @@ int tvam_plan_set_volumes(tvam_plan* plan, const float* volumes);
    rays (telecentric / lens: tvam_cone.hip; ABI v13). */
 int tvam_plan_path(const tvam_plan* plan);
 
+/* Diagnostics: the instantiation of the voxel-driven forward kernel that the plan launches (the
+   launcher dispatches on the same record).  v[8] = slices per workgroup Z, candidate columns NC the
+   kernel is instantiated for, the plan's candidate count nc (1 is served by NC = 2; behind a
+   refracting vial the largest per-(tile, angle) count), staged window columns ncmax, angles per
+   barrier AB, staged values (binned: float4s) per thread PF, flags (bit 0 BIN: staged from the
+   slice-binned patterns, 1 DMA: by LDS-DMA, 2 MULTI: the direct staging sums several DMD rows per
+   slice, 3 REFR: refracted chords, 4 SCONST: per-angle constants in scalar registers), angle parts
+   per (tile, slice chunk).  TVAM_ERR_UNSUPPORTED when the voxel-driven forward does not serve the
+   plan (tvam_plan_path bit 1 clear).  (Added to ABI v13: no struct or existing signature changed.) */
+int tvam_plan_fwd_variant(const tvam_plan* plan, int32_t* v);
+
 /*
  * Fused vector kernels of the linear L-BFGS step (lbfgs.py:146-275,
  * optimize.py:316-318).  All vectors are f32, n entries, 16-byte aligned.

@@ -64,19 +64,46 @@ def test_desc_defaults_follow_reference():
     ("film_channels", 3, "film_channels"),
     ("albedo", 0.5, "scattering"),
     ("abi_version", 99, "abi_version"),
+    # transmission_only = 0 behind a refracting vial: the reference then samples reflection at the glass
+    # interfaces (volume.py:235-243), the kernels only refract; refused by name (TVAM_ERR_UNSUPPORTED)
+    ("vial_type", _abi.VIAL_CYLINDRICAL, "transmission_only = 0 behind a 'cylindrical' vial"),
+    ("vial_type", _abi.VIAL_SQUARE, "transmission_only = 0 behind a 'square' vial"),
 ])
 def test_plan_create_rejects_invalid_desc(field, value, msg):
     lib = _abi.load_library()
     d = _abi.default_desc()
     d.vial_r = 8.0
+    if "transmission_only" in msg:
+        d.transmission_only, d.vial_r_ext, d.vial_ior, d.medium_ior = 0, 9.0, 1.54, 1.4
     setattr(d, field, value)
     plan = ctypes.c_void_p()
     rc = lib.tvam_plan_create(ctypes.byref(d), 0, ctypes.byref(plan))
     assert rc in (_abi.TVAM_ERR_INVALID, _abi.TVAM_ERR_UNSUPPORTED)
+    if "transmission_only" in msg:
+        assert rc == _abi.TVAM_ERR_UNSUPPORTED
     assert not plan.value
     assert msg in lib.tvam_last_error().decode()
     with pytest.raises(ValueError, match=msg):
         _abi.check(rc)
+
+
+def test_index_matched_validation_ignores_transmission_only():
+    """An index-matched vial has no dielectric interface: transmission_only = 0 passes validation
+    (the remaining descriptor is refused for its own fault, a crop beyond the DMD)."""
+    lib = _abi.load_library()
+    d = _abi.default_desc()
+    d.vial_r, d.transmission_only, d.crop_x = 8.0, 0, 300
+    plan = ctypes.c_void_p()
+    rc = lib.tvam_plan_create(ctypes.byref(d), 0, ctypes.byref(plan))
+    assert rc == _abi.TVAM_ERR_INVALID and not plan.value
+    assert "Crop resolution" in lib.tvam_last_error().decode()
+
+
+def test_fwd_variant_rejects_null_arguments():
+    lib = _abi.load_library()
+    v = (ctypes.c_int32 * 8)()
+    assert lib.tvam_plan_fwd_variant(None, v) == _abi.TVAM_ERR_INVALID
+    assert lib.tvam_last_error()
 
 
 def test_round4_vector_entry_points_validate_before_hip():
