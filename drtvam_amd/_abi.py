@@ -26,6 +26,7 @@ PROJECTOR_LENS = 2
 VIAL_INDEX_MATCHED = 0
 VIAL_CYLINDRICAL = 1
 VIAL_SQUARE = 2
+VIAL_CUSTOM = 3
 PHASE_ISOTROPIC = 0
 PHASE_RAYLEIGH = 1
 PHASE_HG = 2
@@ -99,7 +100,7 @@ class TvamDesc(ctypes.Structure):
     def copy(self) -> "TvamDesc":
         d = TvamDesc()
         ctypes.pointer(d)[0] = self
-        for keep in ("_occluders", "_targets"):  # keep the triangle arrays alive with the copy
+        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner"):  # the triangle arrays go with the copy
             if hasattr(self, keep):
                 setattr(d, keep, getattr(self, keep))
         return d
@@ -120,6 +121,14 @@ class TvamDesc(ctypes.Structure):
         self.occluder_tris = t.ctypes.data if t.size else None
         self.n_occluder_tris = int(t.shape[0])
 
+    def set_vial_meshes(self, outer, inner) -> None:
+        """Outer and inner surface of a 'custom' vial, triangles [n][3][3] (float32, host, world space,
+        wound outwards).  They are not part of the C struct: engine.Projection hands them to
+        tvam_plan_create_mesh."""
+        import numpy as np
+        self._vial_outer = np.ascontiguousarray(outer, dtype=np.float32).reshape(-1, 3, 3)
+        self._vial_inner = np.ascontiguousarray(inner, dtype=np.float32).reshape(-1, 3, 3)
+
     def as_dict(self) -> dict:
         out = {}
         for name, _ in self._fields_:
@@ -133,6 +142,9 @@ _P = ctypes.c_void_p
 EXPORTS = {
     "tvam_desc_init": (None, [ctypes.POINTER(TvamDesc)]),
     "tvam_plan_create": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.c_int, ctypes.POINTER(_P)]),
+    "tvam_plan_create_mesh": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P, ctypes.c_int32, _P, ctypes.c_int32,
+                                             ctypes.c_int, ctypes.POINTER(_P)]),
+    "tvam_mesh_hit": (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
     "tvam_plan_destroy": (None, [_P]),
     "tvam_forward": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_adjoint": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
@@ -256,6 +268,22 @@ def check(rc: int) -> None:
     if rc == TVAM_ERR_TOO_LARGE:
         raise Exception(msg)
     raise TvamError(msg)
+
+
+def mesh_hit(tris, o, d, use_bvh: bool = True):
+    """Closest hit of rays (o, d: [n, 3]) with the triangles [m][3][3] on the host (tvam_mesh_hit):
+    (t float32 [n], +inf where none; tri int32 [n], -1 where none).  No GPU is touched."""
+    import numpy as np
+    tris = np.ascontiguousarray(tris, dtype=np.float32).reshape(-1, 3, 3)
+    o = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("mesh_hit: o and d must have the same shape")
+    t = np.empty(o.shape[0], np.float32)
+    tri = np.empty(o.shape[0], np.int32)
+    check(load_library().tvam_mesh_hit(tris.ctypes.data if tris.size else None, tris.shape[0], o.ctypes.data,
+                                       d.ctypes.data, o.shape[0], 1 if use_bvh else 0, t.ctypes.data, tri.ctypes.data))
+    return t, tri
 
 
 def default_desc() -> TvamDesc:

@@ -164,6 +164,22 @@ BOX_HOLE_CYLINDRICAL = {
     "n_steps": 30,
 }
 
+# tests/files/box_hole_custom_cuvette.json of the reference (data, restated; the vial mesh and
+# target paths are set by the caller): a rectangular glass cuvette given as two PLY meshes
+BOX_HOLE_CUSTOM_CUVETTE = {
+    "vial": {"type": "custom", "filename_vial_outer": "tests/files/cuvette_outer.ply",
+             "filename_vial_inner": "tests/files/cuvette_inner.ply", "ior": 1.4702,
+             "medium": {"ior": 1.33, "phase": {"type": "rayleigh"}, "extinction": 0.06, "albedo": 0.0}},
+    "projector": {"type": "telecentric", "n_patterns": 200, "resx": 200, "resy": 20, "pixel_size": 50e-3,
+                  "motion": "circular", "distance": 20, "focus_distance": 20, "aperture_radius": 0.01},
+    "sensor": {"type": "dda", "scalex": 5, "scaley": 5, "scalez": 1.25,
+               "film": {"type": "vfilm", "resx": 100, "resy": 100, "resz": 50}},
+    "target": {"filename": "tests/files/box_hole.ply", "size": 4.0},
+    "loss": {"type": "threshold", "tl": 0.9, "tu": 0.97},
+    "progressive": True,
+    "n_steps": 35,
+}
+
 
 def desc_from_config(config, angle_range=None, tile: int = 0) -> _abi.TvamDesc:
     """tvam_desc of a config through the plugin classes (no GPU needed)."""

@@ -451,8 +451,9 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
                               uint32_t seed, float* rays, void* stream_) {
     if (!p || (!rays && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     const tvam_desc& d = p->desc;
-    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED || d.albedo != 0.0f || d.n_occluder_tris > 0)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched plans without scattering or occluders only");
+    if ((d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM) || d.albedo != 0.0f ||
+        d.n_occluder_tris > 0)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched and 'custom' vial plans without scattering or occluders only");
     hipStream_t stream = (hipStream_t)stream_;
     TvamConsts k;
     int rc = call_setup(p, n_active, active_pixels, spp, k);
@@ -505,6 +506,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
                           int32_t max_depth, float* radon, void* stream_) {
     if (!p || !radon || n_target_tris < 0 || (n_target_tris > 0 && !target_tris))
         return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->mesh)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'custom' vial with filter_radon is not implemented on the GPU path");
     if (p->cone)  // the Radon path is a planar ray (tvam_radon_ray)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "the 'telecentric' / 'lens' projectors with filter_radon are not implemented on the GPU path");
     TvamConsts k;

@@ -42,6 +42,15 @@ __device__ __forceinline__ float tvam_omexp(float x) {
     return 1.0f - __builtin_amdgcn_exp2f(TVAM_NLOG2E * x);
 }
 
+// A 'custom' vial's surfaces (tvam_mesh.h): both meshes under one bounding volume hierarchy.
+struct TvamMesh {
+    const float4* nodes;  // [2 n_nodes] depth-first: {box lo, skip index bits}, {box hi, first | count << 28 bits}
+    const float* tris;    // [n_tris][3][3] in leaf order
+    const int32_t* ids;   // [n_tris] index in the caller's order, inner mesh first: id < n_inner = inner mesh
+    int32_t n_nodes, n_tris, n_inner;
+    int32_t lds_bytes;    // > 0: the three tables fit the kernels' LDS staging budget (their bytes)
+};
+
 struct TvamConsts {
     // film / sensor (sensor.py:14-19, film.py:9-14)
     float bmin[3], bmax[3], h[3];
@@ -88,6 +97,7 @@ struct TvamConsts {
     float ap_r;           // 'aperture_radius'
     float focus;          // 'focus_distance'
     float dist;           // 'distance' (camera-space z = 0: the aperture plane)
+    TvamMesh mesh;        // 'custom' vial (vial_type 3), else zeroes
 };
 
 // --------------------------------------------------------------------------

@@ -14,6 +14,12 @@
 //   tvam_cone_emit_kernel   one brick-bin record per ray for tvam_scatter_binned (the binned
 //                     forward: bin fill, sort, tvam_bin_march_kernel and the bin cache)
 //   tvam_cone_export_kernel the rays themselves (tvam_plan_rays)
+//
+// A 'custom' vial (mesh interfaces, tvam_mesh.h) runs the same kernels for all three projectors,
+// instantiated with MESH: the segment comes from cn_segment_mesh (closest hits through the
+// hierarchy, from global memory or from the workgroup's LDS copy), the march takes the refracted
+// direction d2 and the weight em * att.  The index-matched instantiations (MESH = CN_NO_MESH) read
+// d and em as before.
 #include "tvam_internal.h"
 
 #include <algorithm>
@@ -23,10 +29,14 @@
 namespace {
 
 // The ray of flat index ix (cn_ray_at, tvam_cone_ray.h).
+template <int MESH>
 __device__ __forceinline__ bool cn_ray(const TvamConsts& k, const TvamTiles& tp, const int32_t* idxmap,
-                                       const TvamPathIndex& ix, ConeRay& r) {
-    return cn_ray_at(k, tp, ix.al, ix.colc, ix.rowc, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), r);
+                                       const TvamPathIndex& ix, ConeRay& r, const TvamMeshView& mesh) {
+    return cn_ray_at<MESH>(k, tp, ix.al, ix.colc, ix.rowc, tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), r, &mesh);
 }
+
+// the workgroup's LDS copy of the meshes (CN_MESH_LDS launches pass cn_mesh_lds_bytes of dynamic LDS)
+extern __shared__ float4 cn_mesh_lds[];
 
 // The segment's DDA (sensor.py:327-438), stepped like the oracle's or_dda op for op in fp32: the
 // box clip, start / end voxel, dtmax / tstep per axis, then per visit dt = min(dtmax, remaining),
@@ -98,7 +108,7 @@ __device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], c
     return acc;
 }
 
-template <int MODE>
+template <int MODE, int MESH>
 __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
                                                         const int32_t* __restrict__ idxmap,
                                                         const float* __restrict__ gin, float* __restrict__ out,
@@ -107,6 +117,7 @@ __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles 
     const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * spp;
     uint64_t nvis = 0;
     const bool f32 = false;  // (the 64-bit decode alone: the second one costs this kernel its 7th wave/SIMD)
+    const TvamMeshView mesh = cn_mesh_view<MESH>(k, cn_mesh_lds);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
         float em;
@@ -114,11 +125,19 @@ __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles 
         if (!tvam_path_gate<MODE>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
         tvam_path_pixel(k, f32, ix);
         ConeRay r;
-        if (!cn_ray(k, tp, idxmap, ix, r)) continue;
-        const float acc = cn_dda<MODE>(k, r.o2, r.d, r.maxt, em, out, gin, nvis);
-        if (MODE == TVAM_MODE_ADJ) {
-            if (spp == 1) out[act] = acc * k.wscale;  // the entry's only ray: no atomic
-            else if (acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
+        if (!cn_ray<MESH>(k, tp, idxmap, ix, r, mesh)) continue;
+        if (MESH == CN_NO_MESH) {
+            const float acc = cn_dda<MODE>(k, r.o2, r.d, r.maxt, em, out, gin, nvis);
+            if (MODE == TVAM_MODE_ADJ) {
+                if (spp == 1) out[act] = acc * k.wscale;  // the entry's only ray: no atomic
+                else if (acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
+            }
+        } else {
+            const float acc = cn_dda<MODE>(k, r.o2, r.d2, r.maxt, em * r.att, out, gin, nvis) * r.att;
+            if (MODE == TVAM_MODE_ADJ) {
+                if (spp == 1) out[act] = acc * k.wscale;
+                else if (acc != 0.0f) atomicAdd(&out[act], acc * k.wscale);
+            }
         }
     }
     if (MODE == TVAM_MODE_COUNT) tvam_count_reduce(nvis, counter);
@@ -127,10 +146,12 @@ __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles 
 // One brick-bin record per ray of paths [sb.p0, sb.p1) (sb.slots = 1; the layout of
 // tvam_scatter_kernel<EMIT>'s records: weight em, attenuation 1 for the cached forward's rescale,
 // 0 in slots without a segment), its brick count and the chunk's largest |weight|.
+template <int MESH>
 __global__ __launch_bounds__(256) void tvam_cone_emit_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
                                                              const int32_t* __restrict__ idxmap, TvamSegBuf sb) {
     float wmax = 0.0f;
     const bool f32 = tvam_path_fits32(sb.p1);
+    const TvamMeshView mesh = cn_mesh_view<MESH>(k, cn_mesh_lds);
     for (int64_t i = sb.p0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < sb.p1;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t slot = i - sb.p0;
@@ -141,13 +162,15 @@ __global__ __launch_bounds__(256) void tvam_cone_emit_kernel(TvamConsts k, TvamT
         if (!tvam_path_gate<TVAM_MODE_FWD>(k, pat, idxmap, ix.local, k.wscale, k.inv_vol, em, act)) continue;
         tvam_path_pixel(k, f32, ix);
         ConeRay r;
-        if (!cn_ray(k, tp, idxmap, ix, r)) continue;
+        if (!cn_ray<MESH>(k, tp, idxmap, ix, r, mesh)) continue;
         SegDda q;
-        if (!sc_dda_init(k, r.o2, r.d, r.maxt, q)) continue;
+        if (!sc_dda_init(k, r.o2, MESH == CN_NO_MESH ? r.d : r.d2, r.maxt, q)) continue;
+        const float att = MESH == CN_NO_MESH ? 1.0f : r.att;  // (.z: the cached forward's rescale)
+        if (MESH != CN_NO_MESH) em = em * att;
         sb.r[TVAM_REC_F4 * slot] = make_float4(q.t_start, q.tau_end, q.dtm0[0], q.dtm0[1]);
         sb.r[TVAM_REC_F4 * slot + 1] = make_float4(q.dtm0[2], q.ts[0] * (float)q.step[0], q.ts[1] * (float)q.step[1],
                                                    q.ts[2] * (float)q.step[2]);
-        sb.r[TVAM_REC_F4 * slot + 2] = make_float4(__int_as_float(q.sv[0] | (q.sv[1] << 11) | (q.sv[2] << 22)), em, 1.0f, 0.0f);
+        sb.r[TVAM_REC_F4 * slot + 2] = make_float4(__int_as_float(q.sv[0] | (q.sv[1] << 11) | (q.sv[2] << 22)), em, att, 0.0f);
         sb.m[slot] = (uint32_t)sc_brick_count(k, q);
         wmax = fmaxf(wmax, fabsf(em));
     }
@@ -155,12 +178,14 @@ __global__ __launch_bounds__(256) void tvam_cone_emit_kernel(TvamConsts k, TvamT
 }
 
 // tvam_plan_rays: row act * spp + smp = o[3], d[3], hit, o2[3], maxt, d2[3], weight, 0
+template <int MESH>
 __global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, TvamTiles tp,
                                                                const int32_t* __restrict__ idxmap,
                                                                float* __restrict__ rays) {
     const int spp = (int)tp.spp;
     const int64_t n = (int64_t)tp.n_shard * k.crop_y * k.crop_x * spp;
     const bool f32 = tvam_path_fits32(n);
+    const TvamMeshView mesh = cn_mesh_view<MESH>(k, cn_mesh_lds);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         TvamPathIndex ix = tvam_path_index<false>(k, tp, i, f32);
         float em;
@@ -170,44 +195,84 @@ __global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, Tva
         ConeRay r;
         r.o2[0] = r.o2[1] = r.o2[2] = 0.0f;
         r.maxt = 0.0f;
-        const bool hit = cn_ray(k, tp, idxmap, ix, r);
+        const bool hit = cn_ray<MESH>(k, tp, idxmap, ix, r, mesh);
+        if (MESH == CN_NO_MESH || !hit) {  // (a ray that never reaches the medium keeps its own direction)
+            r.d2[0] = r.d[0], r.d2[1] = r.d[1], r.d2[2] = r.d[2];
+            r.att = 1.0f;
+        }
         float4* row = reinterpret_cast<float4*>(rays + 16 * (act * spp + ix.smp));
         row[0] = make_float4(r.o[0], r.o[1], r.o[2], r.d[0]);
         row[1] = make_float4(r.d[1], r.d[2], hit ? 1.0f : 0.0f, hit ? r.o2[0] : 0.0f);
-        row[2] = make_float4(hit ? r.o2[1] : 0.0f, hit ? r.o2[2] : 0.0f, hit ? r.maxt : 0.0f, r.d[0]);
-        row[3] = make_float4(r.d[1], r.d[2], k.wscale, 0.0f);
+        row[2] = make_float4(hit ? r.o2[1] : 0.0f, hit ? r.o2[2] : 0.0f, hit ? r.maxt : 0.0f, r.d2[0]);
+        row[3] = make_float4(r.d2[1], r.d2[2], MESH == CN_NO_MESH ? k.wscale : k.wscale * r.att, 0.0f);
     }
 }
 
 }  // namespace
 
-hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
-                                 const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
-                                 hipStream_t stream) {
+// MESH of a launch and its dynamic LDS.
+static int cn_mesh_mode(const TvamConsts& k) {
+    return k.vial_type != TVAM_VIAL_CUSTOM ? CN_NO_MESH : (k.mesh.lds_bytes > 0 ? CN_MESH_LDS : CN_MESH_GLOBAL);
+}
+static size_t cn_lds(const TvamConsts& k) { return cn_mesh_mode(k) == CN_MESH_LDS ? cn_mesh_lds_bytes(k.mesh) : 0; }
+
+template <int MESH>
+static void cn_launch_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
+                           const float* gin, float* out, unsigned long long* counter, hipStream_t stream) {
     const dim3 g(tvam_grid_1d((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp, 262144)), b(256);
+    const size_t lds = cn_lds(k);
     switch (mode) {
         case TVAM_MODE_FWD:
             tvam_kt_begin(stream, TVAM_KT_CONE);
-            hipLaunchKernelGGL(tvam_cone_kernel<TVAM_MODE_FWD>, g, b, 0, stream, k, t, pat, idxmap, gin, out, counter);
+            hipLaunchKernelGGL((tvam_cone_kernel<TVAM_MODE_FWD, MESH>), g, b, lds, stream, k, t, pat, idxmap, gin, out,
+                               counter);
             tvam_kt_end(stream, TVAM_KT_CONE);
             break;
         case TVAM_MODE_ADJ:
-            hipLaunchKernelGGL(tvam_cone_kernel<TVAM_MODE_ADJ>, g, b, 0, stream, k, t, pat, idxmap, gin, out, counter);
+            hipLaunchKernelGGL((tvam_cone_kernel<TVAM_MODE_ADJ, MESH>), g, b, lds, stream, k, t, pat, idxmap, gin, out,
+                               counter);
             break;
         default:
-            hipLaunchKernelGGL(tvam_cone_kernel<TVAM_MODE_COUNT>, g, b, 0, stream, k, t, pat, idxmap, gin, out, counter);
+            hipLaunchKernelGGL((tvam_cone_kernel<TVAM_MODE_COUNT, MESH>), g, b, lds, stream, k, t, pat, idxmap, gin, out,
+                               counter);
+    }
+}
+
+hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                                 const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
+                                 hipStream_t stream) {
+    switch (cn_mesh_mode(k)) {
+        case CN_NO_MESH: cn_launch_rays<CN_NO_MESH>(mode, k, t, pat, idxmap, gin, out, counter, stream); break;
+        case CN_MESH_LDS: cn_launch_rays<CN_MESH_LDS>(mode, k, t, pat, idxmap, gin, out, counter, stream); break;
+        default: cn_launch_rays<CN_MESH_GLOBAL>(mode, k, t, pat, idxmap, gin, out, counter, stream);
     }
     return hipGetLastError();
 }
 
 void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
                              const TvamSegBuf& sb, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(tvam_cone_emit_kernel, dim3(grid), dim3(256), 0, stream, k, t, pat, idxmap, sb);
+    const dim3 g(grid), b(256);
+    switch (cn_mesh_mode(k)) {
+        case CN_NO_MESH:
+            hipLaunchKernelGGL(tvam_cone_emit_kernel<CN_NO_MESH>, g, b, 0, stream, k, t, pat, idxmap, sb);
+            break;
+        case CN_MESH_LDS:
+            hipLaunchKernelGGL(tvam_cone_emit_kernel<CN_MESH_LDS>, g, b, cn_lds(k), stream, k, t, pat, idxmap, sb);
+            break;
+        default:
+            hipLaunchKernelGGL(tvam_cone_emit_kernel<CN_MESH_GLOBAL>, g, b, 0, stream, k, t, pat, idxmap, sb);
+    }
 }
 
 hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
                                    hipStream_t stream) {
     const dim3 g(tvam_grid_1d((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp, 262144)), b(256);
-    hipLaunchKernelGGL(tvam_cone_export_kernel, g, b, 0, stream, k, t, idxmap, rays);
+    switch (cn_mesh_mode(k)) {
+        case CN_NO_MESH: hipLaunchKernelGGL(tvam_cone_export_kernel<CN_NO_MESH>, g, b, 0, stream, k, t, idxmap, rays); break;
+        case CN_MESH_LDS:
+            hipLaunchKernelGGL(tvam_cone_export_kernel<CN_MESH_LDS>, g, b, cn_lds(k), stream, k, t, idxmap, rays);
+            break;
+        default: hipLaunchKernelGGL(tvam_cone_export_kernel<CN_MESH_GLOBAL>, g, b, 0, stream, k, t, idxmap, rays);
+    }
     return hipGetLastError();
 }

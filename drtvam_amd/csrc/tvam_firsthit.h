@@ -8,6 +8,7 @@
 //   index_matched   open tube of radius vial_r, |z| <= vial_half_h
 //   cylindrical     open tube of radius vial_r_ext, |z| <= vial_half_h
 //   square          closed cuboid vial_r_ext x vial_r_ext x vial_half_h (all six faces)
+//   custom          the outer mesh, from either side (tvam_mesh.h)
 //
 // A tube is hit from either side (si.is_valid() does not look at the orientation): a ray that
 // came in through an open end and meets the inside wall has a valid hit.  The reference's scene
@@ -15,6 +16,7 @@
 // so it is left out here (the one deviation).
 #pragma once
 #include "tvam_common.h"
+#include "tvam_mesh.h"
 
 struct TvamFirstHit {
     float t;            // distance along the ray, -1: no surface
@@ -35,6 +37,10 @@ TVAM_HD float tvam_tube_hit3(float ox, float oy, float oz, float dx, float dy, f
 
 // The container's outer surface alone.
 TVAM_HD float tvam_outer_hit(const TvamConsts& k, float ox, float oy, float oz, float dx, float dy, float dz) {
+    if (k.vial_type == 3 /* TVAM_VIAL_CUSTOM */) {
+        int slot;
+        return tvam_mesh_closest(tvam_mesh_view(k.mesh), TVAM_MESH_OUTER, ox, oy, oz, dx, dy, dz, slot);
+    }
     if (k.vial_type == 2 /* TVAM_VIAL_SQUARE */) {
         float nx, ny, nz;
         return tvam_box_hit(ox, oy, oz, dx, dy, dz, k.vial_r_ext, k.vial_r_ext, k.vial_half_h, nx, ny, nz);

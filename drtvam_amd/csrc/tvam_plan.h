@@ -40,8 +40,12 @@ struct tvam_plan {
     bool surface = false;    // surface-aware film (2 channels): per-path kernels cut at the target mesh
     bool general = false;    // sample_time or a ratio / delta sensor: the general per-path kernel
     bool cone = false;       // telecentric / lens projector: 3-D first segments (tvam_cone.hip); implies general
+    bool mesh = false;       // 'custom' vial: mesh interfaces traced per ray (tvam_mesh.h); implies cone
     const float* vols = nullptr;  // caller's compute_volume() output (tvam_plan_set_volumes)
     TvamDevBuf<float> tgt, occ;   // target mesh (surface-aware films) and occluder triangles
+    TvamDevBuf<float4> mesh_nodes;  // 'custom' vial: the hierarchy over both meshes (TvamMesh)
+    TvamDevBuf<float> mesh_tris;
+    TvamDevBuf<int32_t> mesh_ids;
     // device tables (TvamTiles)
     TvamDevBuf<float2> cs;
     TvamDevBuf<int32_t> slice_off, slice_rows;
@@ -98,6 +102,7 @@ struct tvam_plan {
     // nothing gives nullptr.  (pl.chord and the visit lists' pl.adjl_* are set by their builders.)
     void bind() {
         k.tgt = tgt.get(), k.occ = occ.get();
+        k.mesh.nodes = mesh_nodes.get(), k.mesh.tris = mesh_tris.get(), k.mesh.ids = mesh_ids.get();
         tiles.cs = cs.get(), tiles.ang = ang.get();
         tiles.slice_off = slice_off.get(), tiles.slice_rows = slice_rows.get();
         tiles.slots = slots.get(), tiles.slot_off = slot_off.get();

@@ -8,6 +8,7 @@
 //   * per-z-slice list of DMD rows whose (planar) rays lie in that slice;
 //   * per-(xy-tile, angle) range of DMD columns whose rays can cross the tile.
 #include "tvam_plan.h"
+#include "tvam_mesh.h"
 
 #include <algorithm>
 #include <mutex>
@@ -84,7 +85,28 @@ static int validate(const tvam_desc& d) {
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED && d.projector_type != TVAM_PROJECTOR_TELECENTRIC &&
         d.projector_type != TVAM_PROJECTOR_LENS)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'collimated', 'telecentric' and 'lens' projectors are implemented on the GPU path");
-    if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
+    if (d.vial_type == TVAM_VIAL_CUSTOM) {
+        // mesh vial (tvam_plan_create_mesh): every ray is traced in 3-D through the interfaces and
+        // runs the per-ray kernels of tvam_cone.hip, whose limits these are
+        auto no = [&](const char* what) {
+            return tvam_fail(TVAM_ERR_UNSUPPORTED,
+                             std::string("a 'custom' vial with ") + what + " is not implemented on the GPU path");
+        };
+        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
+            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
+            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
+        }
+        if (d.n_occluder_tris > 0) return no("occluders");
+        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
+        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
+        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
+        if (d.film_channels == 2) return no("a surface-aware film");
+        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
+        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
+        if (d.rr_depth < 2) return no("rr_depth < 2 (Russian roulette before the medium segment)");
+        if (!(d.vial_ior > 0.0f && d.medium_ior > 0.0f))
+            return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs positive IORs");
+    } else if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
         // 3-D projector rays (tvam_cone.hip): index-matched vial, absorbing medium, 'dda' sensor,
         // one-channel film, the whole film
         const char* pn = d.projector_type == TVAM_PROJECTOR_LENS ? "'lens'" : "'telecentric'";
@@ -115,8 +137,8 @@ static int validate(const tvam_desc& d) {
         (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "sample_time and the ratio / delta sensors need a film without slabs");
     if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CYLINDRICAL &&
-        d.vial_type != TVAM_VIAL_SQUARE)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'index_matched', 'cylindrical' and 'square' containers are implemented on the GPU path");
+        d.vial_type != TVAM_VIAL_SQUARE && d.vial_type != TVAM_VIAL_CUSTOM)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'index_matched', 'cylindrical', 'square' and 'custom' containers are implemented on the GPU path");
     // transmission_only = False lets the reference sample reflection as well as refraction at every
     // dielectric interface after the first (volume.py:235-243, radon.py:87-95); the kernels only
     // refract.  An index-matched vial has no such interface.
@@ -156,8 +178,10 @@ static int validate(const tvam_desc& d) {
         if (d.film_res[a] <= 0) return tvam_fail(TVAM_ERR_INVALID, "film resolution must be positive");
         if (!(d.bbox_max[a] > d.bbox_min[a])) return tvam_fail(TVAM_ERR_INVALID, "sensor bounding box is empty");
     }
-    if (!(d.vial_r > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "vial radius must be positive");
-    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED &&
+    // (a 'custom' vial's surfaces are its meshes: vial_r, vial_r_ext and vial_height are unused)
+    if (d.vial_type != TVAM_VIAL_CUSTOM && !(d.vial_r > 0.0f))
+        return tvam_fail(TVAM_ERR_INVALID, "vial radius must be positive");
+    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM &&
         !(d.vial_r_ext > d.vial_r && d.vial_ior > 0.0f && d.medium_ior > 0.0f && d.vial_height > 0.0f))
         return tvam_fail(TVAM_ERR_INVALID, "glass vial: need r_ext > r_int > 0 (w_ext > w_int) and positive IORs");
     {
@@ -1176,12 +1200,60 @@ static int64_t slot_lists(tvam_plan* p, const std::vector<float2>& cs, std::vect
     return max_nrt;
 }
 
+// The hierarchy over both meshes of a 'custom' vial (inner mesh first: a tie in t between the two
+// goes to the inner one, tvam_segment_square's `ti <= te`), uploaded through the plan's owners.
+static int upload_vial_meshes(tvam_plan* p, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner) {
+    std::vector<float> all(inner, inner + 9 * (size_t)n_inner);
+    all.insert(all.end(), outer, outer + 9 * (size_t)n_outer);
+    TvamMeshHost h;
+    tvam_mesh_build(all.data(), n_inner + n_outer, h);
+    // whole 16-byte rows: the kernels' LDS staging copies the tables as float4 (cn_mesh_view)
+    h.tris.resize((h.tris.size() + 3) / 4 * 4, 0.0f);
+    h.ids.resize((h.ids.size() + 3) / 4 * 4, 0);
+    int rc;
+    if ((rc = tvam_upload(p->mesh_nodes, h.nodes)) || (rc = tvam_upload(p->mesh_tris, h.tris)) ||
+        (rc = tvam_upload(p->mesh_ids, h.ids)))
+        return rc;
+    TvamMesh& m = p->k.mesh;
+    m.n_nodes = (int32_t)(h.nodes.size() / 2);
+    m.n_tris = n_inner + n_outer;
+    m.n_inner = n_inner;
+    const size_t bytes = h.nodes.size() * sizeof(float4) + h.tris.size() * sizeof(float) + h.ids.size() * sizeof(int32_t);
+    m.lds_bytes = bytes <= TVAM_MESH_LDS_BUDGET ? (int32_t)bytes : 0;
+    p->bind();
+    return 0;
+}
+
+static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
+                       int device, tvam_plan** out);
+
 extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** out) {
     if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_CUSTOM)
+        return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs its meshes: create the plan with tvam_plan_create_mesh");
+    return plan_create(*desc, nullptr, 0, nullptr, 0, device, out);
+}
+
+extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_t n_outer,
+                                     const float* inner_tris, int32_t n_inner, int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type != TVAM_VIAL_CUSTOM)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_mesh: vial_type must be TVAM_VIAL_CUSTOM");
     int rc = validate(*desc);
     if (rc) return rc;
-    const tvam_desc& d = *desc;
+    if ((rc = tvam_mesh_validate("outer", outer_tris, n_outer)) || (rc = tvam_mesh_validate("inner", inner_tris, n_inner)))
+        return rc;
+    if ((int64_t)n_outer + n_inner >= (1 << 27))
+        return tvam_fail(TVAM_ERR_TOO_LARGE, "the vial meshes have too many triangles");
+    return plan_create(*desc, outer_tris, n_outer, inner_tris, n_inner, device, out);
+}
+
+static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
+                       int device, tvam_plan** out) {
+    int rc = validate(d);
+    if (rc) return rc;
     int a0 = d.angle_begin, a1 = d.angle_end < 0 ? d.n_patterns : d.angle_end;
     if (a0 < 0 || a1 > d.n_patterns || a0 > a1) return tvam_fail(TVAM_ERR_INVALID, "invalid angle shard");
 
@@ -1200,9 +1272,12 @@ extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** o
     // surfaces + medium segment (volume.py:179, :271-272)
     p->empty = d.max_depth < (p->cyl ? 3 : 2);
     p->surface = d.film_channels == 2;
-    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED;
+    p->mesh = d.vial_type == TVAM_VIAL_CUSTOM;
+    if (p->mesh) p->empty = d.max_depth < 3;  // two glass surfaces + the medium segment, like the glass vials
+    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh;
     p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
     if ((rc = upload_meshes(p.get())) || (rc = tile_geometry(p.get()))) return rc;
+    if (p->mesh && (rc = upload_vial_meshes(p.get(), outer, n_outer, inner, n_inner))) return rc;
 
     std::vector<float2> cs;
     std::vector<float4> ang;
@@ -1284,6 +1359,8 @@ extern "C" int tvam_row_slices(const tvam_desc* desc, int32_t* slice_of_row) {
     const tvam_desc& d = *desc;
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED)  // 3-D rays cross slices: no row <-> slice map
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: the 'telecentric' / 'lens' projectors' rays leave their slice (no film slabs)");
+    if (d.vial_type == TVAM_VIAL_CUSTOM)  // refracted at tilted faces, they leave it too
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: a 'custom' vial's rays leave their slice (no film slabs)");
     const TvamConsts k = make_consts(d, 0, d.n_patterns);
     for (int r = 0; r < d.crop_y; ++r) {
         float xc, yc;

@@ -50,7 +50,16 @@ class Projection:
             self.device = torch.device("cuda", torch.cuda.current_device())
         plan = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _abi.check(self.lib.tvam_plan_create(ctypes.byref(self.desc), self.device.index, ctypes.byref(plan)))
+            if self.desc.vial_type == _abi.VIAL_CUSTOM:  # the meshes travel beside the struct (set_vial_meshes)
+                outer = getattr(self.desc, "_vial_outer", None)
+                inner = getattr(self.desc, "_vial_inner", None)
+                _abi.check(self.lib.tvam_plan_create_mesh(
+                    ctypes.byref(self.desc), None if outer is None or not outer.size else outer.ctypes.data,
+                    0 if outer is None else int(outer.shape[0]),
+                    None if inner is None or not inner.size else inner.ctypes.data,
+                    0 if inner is None else int(inner.shape[0]), self.device.index, ctypes.byref(plan)))
+            else:
+                _abi.check(self.lib.tvam_plan_create(ctypes.byref(self.desc), self.device.index, ctypes.byref(plan)))
         self._plan = plan
         rx, ry, rz = self.desc.film_res
         if self.desc.slab_end >= 0:  # film slab of this plan (z-slab sharding)
@@ -221,7 +230,8 @@ class Projection:
         """The projector rays of a call (tvam_plan_rays), [n_active * spp, 16] float32 in sampler-stream
         order (row = active entry * spp + sample): o[0:3], d[3:6], hit [6], o2[7:10], maxt [10],
         d2[11:14], weight [14] (the whole per-ray weight), 0.  The diagnostic counterpart of the
-        oracle's ray(); index-matched plans with a non-scattering medium."""
+        oracle's ray(); index-matched plans with a non-scattering medium, and 'custom' vial plans
+        (d2: the refracted direction; the weight carries the interfaces' transmission)."""
         if active_pixels is not None:
             self._check_pixels(active_pixels)
             n_active = int(active_pixels.numel())
@@ -239,7 +249,7 @@ class Projection:
 
     @property
     def cone(self) -> bool:
-        """True for the 3-D projector rays of a telecentric / lens projector."""
+        """True for the 3-D per-ray path: a telecentric / lens projector, or a 'custom' vial."""
         return bool(self.lib.tvam_plan_path(self._plan) & 4)
 
     @property

@@ -186,8 +186,27 @@ class CustomVial(Container):
 
     def to_dict(self):
         return {'printing_medium': self.medium_dict(),
-                'vial_exterior': {'type': 'ply', 'filename': self.filename_vial_outer},
-                'vial_interior': {'type': 'ply', 'filename': self.filename_vial_inner}}
+                'vial_exterior': {'type': 'ply', 'face_normals': True, 'filename': self.filename_vial_outer,
+                                  'bsdf': {'type': 'dielectric', 'int_ior': self.vial_ior, 'ext_ior': 'air'}},
+                'vial_interior': {'type': 'ply', 'filename': self.filename_vial_inner, 'face_normals': True,
+                                  'bsdf': {'type': 'dielectric', 'ext_ior': self.vial_ior, 'int_ior': self.medium_ior},
+                                  'interior': {'type': 'ref', 'id': 'printing_medium'}}}
+
+    def fill_desc(self, desc):
+        """Both PLYs as world-space triangles (face normals from the winding: both surfaces must be
+        wound outwards, geometry.py:106-107), handed to the plan beside the descriptor."""
+        if self.occlusions:
+            raise NotImplementedError("a 'custom' vial with occluders is not implemented on the GPU path")
+        import numpy as np
+        from .utils import read_ply
+        self._fill_medium(desc)
+        desc.vial_type = _abi.VIAL_CUSTOM
+        desc.vial_ior = lookup_ior(self.vial_ior)
+        tris = []
+        for name in (self.filename_vial_outer, self.filename_vial_inner):
+            v, f = read_ply(name)
+            tris.append(np.asarray(v, np.float32)[np.asarray(f)])
+        desc.set_vial_meshes(tris[0], tris[1])
 
 
 class DoubleCylindricalVial(Container):

@@ -530,7 +530,8 @@ class TvamProblem(ShardedLoop):
         self.crop_x, self.crop_y = p.crop[0], p.crop[1]
         full_desc = VolumeIntegrator(base).desc(self.scene, self.sensor)
         self.res_z = int(full_desc.film_res[2])
-        if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0):
+        custom = int(full_desc.vial_type) == 3  # _abi.VIAL_CUSTOM: mesh interfaces, 3-D per-ray path
+        if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0 or custom):
             # every path marched, as the reference marches every active pixel (projector.py:66-70,
             # common.py:81-82): a scattering scene's paths (and a telecentric / lens projector's
             # binned first segments) then do not depend on the pattern, and
@@ -549,7 +550,12 @@ class TvamProblem(ShardedLoop):
         self.target_full = target.to(dtype=torch.float32)
         # scattered paths leave their slice; surface-aware films run the per-path kernels
         # a telecentric / lens projector's rays cross slices too (3-D first segments)
-        cone = int(full_desc.projector_type) != 0
+        if custom and shard == 'slab':
+            raise ValueError("z-slab sharding needs planar rays: a 'custom' vial's rays are refracted at its mesh "
+                             "faces and leave their slice (use shard 'angle')")
+        if custom and config.get('filter_radon', False) and filter_pixels:
+            raise NotImplementedError("filter_radon with a 'custom' vial is not implemented on the GPU path")
+        cone = int(full_desc.projector_type) != 0 or custom
         if cone and shard == 'slab':
             raise ValueError("z-slab sharding needs planar rays: the 'telecentric' and 'lens' projectors' rays "
                              "leave their slice (use shard 'angle')")

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .geometry import CylindricalVial, IndexMatchedVial, Container
+from .geometry import CustomVial, CylindricalVial, IndexMatchedVial, Container
 from .integrators import integrators, VolumeIntegrator
 from .projector import TVAMProjector, emitters
 from .sensor import VolumetricSensor, sensors
@@ -79,6 +79,13 @@ def _container_from_shapes(scene_dict):
                                     'height': float(abs(p1[2] - p0[2])),
                                     'ior': bsdf.get('ext_ior', 1.5),
                                     'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
+    if shp['type'] == 'ply' and bsdf.get('type') == 'dielectric':  # CustomVial.to_dict: two dielectric meshes
+        outer = [v for k, v in shapes.items() if k != name and v['type'] == 'ply'
+                 and v.get('bsdf', {}).get('type') == 'dielectric']
+        if len(outer) == 1:
+            return CustomVial({'filename_vial_outer': outer[0]['filename'], 'filename_vial_inner': shp['filename'],
+                               'ior': bsdf.get('ext_ior', outer[0]['bsdf'].get('int_ior', 1.5)),
+                               'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
     raise NotImplementedError(f"container shape '{name}' is not supported by the GPU engine")
 
 

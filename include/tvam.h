@@ -63,6 +63,8 @@ extern "C" {
 #define TVAM_VIAL_INDEX_MATCHED   0
 #define TVAM_VIAL_CYLINDRICAL     1
 #define TVAM_VIAL_SQUARE          2  /* glass cuboids w_ext / w_int (vial_r = w_int/2, vial_r_ext = w_ext/2) */
+#define TVAM_VIAL_CUSTOM          3  /* dielectric triangle meshes (tvam_plan_create_mesh; vial_r, vial_r_ext and
+                                        vial_height unused) */
 
 /* medium phase functions (Mitsuba 'isotropic', 'rayleigh', 'hg'; geometry.py:29-39) */
 #define TVAM_PHASE_ISOTROPIC      0
@@ -184,6 +186,33 @@ void tvam_desc_init(tvam_desc* desc);
 /* Validate desc, build per-angle / per-slice / per-tile tables on `device`. */
 int  tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** plan);
 void tvam_plan_destroy(tvam_plan* plan);
+
+/*
+ * A plan behind a 'custom' vial (vial_type = TVAM_VIAL_CUSTOM; geometry.py:98-138): the outer
+ * (air / glass, eta = vial_ior / air) and inner (glass / medium, eta = medium_ior / vial_ior)
+ * surfaces are triangle meshes with dielectric interfaces and face normals
+ * n = normalize((v1 - v0) x (v2 - v0)); the winding decides the side, and both meshes must be
+ * wound outwards.  outer_tris / inner_tris: host arrays [n][3 vertices][x, y, z] in world space,
+ * read here and not kept.  Every ray's path through the interfaces is traced in 3-D (a closest-hit
+ * query against a bounding volume hierarchy built here), so such a plan runs the per-ray 3-D
+ * kernels for all three projectors.  TVAM_ERR_INVALID: null or empty meshes, non-finite vertices,
+ * a zero-area triangle (the message names the mesh and the triangle).  TVAM_ERR_UNSUPPORTED, by
+ * name: occluders, albedo > 0, the ratio / delta sensors, a surface-aware film, film slabs,
+ * transmission_only = 0, rr_depth < 2.  tvam_plan_create refuses TVAM_VIAL_CUSTOM and names this
+ * entry.
+ */
+int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_t n_outer,
+                          const float* inner_tris, int32_t n_inner, int device, tvam_plan** plan);
+
+/*
+ * Closest hit of n_rays rays (o, d: [n_rays][3], host) with a triangle mesh (tris: [n][3][3],
+ * host), on the host with the code the kernels run: t[i] = the nearest hit distance >= 0 (+inf:
+ * none) and tri[i] = its triangle (-1: none); ties in t go to the lower triangle index.
+ * use_bvh = 1 builds the hierarchy a plan builds and traverses it, use_bvh = 0 loops over every
+ * triangle: both return the same t (bit for bit) and tri.  No GPU is touched.
+ */
+int tvam_mesh_hit(const float* tris, int32_t n, const float* o, const float* d, int64_t n_rays, int32_t use_bvh,
+                  float* t, int32_t* tri);
 
 /*
  * Forward projection (primal render).  Writes the whole film
@@ -484,7 +513,9 @@ int tvam_plan_adj_chunk(const tvam_plan* plan);
  * it deposits, its medium segment (o2, d2, [0, maxt]) and its whole weight (inv_pdf / n_samples *
  * print_time * sigma_a / sigma_t; multiply by the pattern value and 1 / voxel volume for the dose).
  * active_pixels as in tvam_forward (NULL: the dense crop order).  All three projector kinds on
- * index-matched plans with a non-scattering medium; TVAM_ERR_UNSUPPORTED otherwise.
+ * index-matched plans with a non-scattering medium, and on 'custom' vial plans, whose d2 is the
+ * refracted direction and whose weight carries the product of the interfaces' transmission
+ * weights; TVAM_ERR_UNSUPPORTED otherwise.
  */
 int tvam_plan_rays(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                    uint32_t seed, float* rays, void* hip_stream);
