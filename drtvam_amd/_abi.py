@@ -27,6 +27,7 @@ VIAL_INDEX_MATCHED = 0
 VIAL_CYLINDRICAL = 1
 VIAL_SQUARE = 2
 VIAL_CUSTOM = 3
+VIAL_DOUBLE_CYLINDRICAL = 4
 PHASE_ISOTROPIC = 0
 PHASE_RAYLEIGH = 1
 PHASE_HG = 2
@@ -41,6 +42,20 @@ FLAG_RAY_FWD = 8
 FLAG_SCATTER_ATOMIC = 16
 FLAG_BIN_FIRST = 32
 LBFGS_WORK_DOUBLES = 2048 * 64
+
+
+class TvamDoubleVial(ctypes.Structure):
+    """tvam_double_vial: the four radii (outermost first) and the glass / core IORs of a
+    'double_cylindrical' vial."""
+    _fields_ = [
+        ("r_ext_outer", ctypes.c_float),
+        ("r_int_outer", ctypes.c_float),
+        ("r_ext_inner", ctypes.c_float),
+        ("r_int_inner", ctypes.c_float),
+        ("ior_outer", ctypes.c_float),
+        ("ior_inner", ctypes.c_float),
+        ("ior_inside_inner", ctypes.c_float),
+    ]
 
 
 class TvamDesc(ctypes.Structure):
@@ -100,7 +115,8 @@ class TvamDesc(ctypes.Structure):
     def copy(self) -> "TvamDesc":
         d = TvamDesc()
         ctypes.pointer(d)[0] = self
-        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner"):  # the triangle arrays go with the copy
+        # the triangle arrays and the double vial go with the copy
+        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner", "_double_vial"):
             if hasattr(self, keep):
                 setattr(d, keep, getattr(self, keep))
         return d
@@ -129,6 +145,14 @@ class TvamDesc(ctypes.Structure):
         self._vial_outer = np.ascontiguousarray(outer, dtype=np.float32).reshape(-1, 3, 3)
         self._vial_inner = np.ascontiguousarray(inner, dtype=np.float32).reshape(-1, 3, 3)
 
+    def set_double_vial(self, r_ext_outer, r_int_outer, r_ext_inner, r_int_inner, ior_outer, ior_inner,
+                        ior_inside_inner) -> None:
+        """Radii and IORs of a 'double_cylindrical' vial.  They are not part of the C struct:
+        engine.Projection hands them to tvam_plan_create_double."""
+        self._double_vial = TvamDoubleVial(float(r_ext_outer), float(r_int_outer), float(r_ext_inner),
+                                           float(r_int_inner), float(ior_outer), float(ior_inner),
+                                           float(ior_inside_inner))
+
     def as_dict(self) -> dict:
         out = {}
         for name, _ in self._fields_:
@@ -145,6 +169,11 @@ EXPORTS = {
     "tvam_plan_create_mesh": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P, ctypes.c_int32, _P, ctypes.c_int32,
                                              ctypes.c_int, ctypes.POINTER(_P)]),
     "tvam_mesh_hit": (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
+    "tvam_plan_create_double": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.POINTER(TvamDoubleVial), ctypes.c_int,
+                                               ctypes.POINTER(_P)]),
+    "tvam_plan_segments": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
+    "tvam_double_segments": (ctypes.c_int, [ctypes.POINTER(TvamDoubleVial), ctypes.c_float, ctypes.c_float,
+                                            ctypes.c_float, ctypes.c_int32, _P, _P, ctypes.c_int64, _P]),
     "tvam_plan_destroy": (None, [_P]),
     "tvam_forward": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_adjoint": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
@@ -284,6 +313,22 @@ def mesh_hit(tris, o, d, use_bvh: bool = True):
     check(load_library().tvam_mesh_hit(tris.ctypes.data if tris.size else None, tris.shape[0], o.ctypes.data,
                                        d.ctypes.data, o.shape[0], 1 if use_bvh else 0, t.ctypes.data, tri.ctypes.data))
     return t, tri
+
+
+def double_segments(vial: TvamDoubleVial, medium_ior, sigma_t, height, max_depth, o, d):
+    """Medium segments of world rays (o, d: [n, 3]) behind a 'double_cylindrical' vial on the host
+    (tvam_double_segments, the kernels' own tracer): float32 [n, 2, 8] = o2[0:3], maxt [3],
+    d2[4:7], attenuation [7]; a slot without a segment is all zeros.  No GPU is touched."""
+    import numpy as np
+    o = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("double_segments: o and d must have the same shape")
+    segs = np.empty((o.shape[0], 2, 8), np.float32)
+    check(load_library().tvam_double_segments(ctypes.byref(vial), float(medium_ior), float(sigma_t), float(height),
+                                              int(max_depth), o.ctypes.data, d.ctypes.data, o.shape[0],
+                                              segs.ctypes.data))
+    return segs
 
 
 def default_desc() -> TvamDesc:

@@ -218,11 +218,11 @@ typedef hipError_t (*TvamPerRay)(int mode, const TvamConsts& k, const TvamTiles&
                                  hipStream_t stream);
 static int scattered_segments(int mode, tvam_plan* p, const TvamConsts& k, const TvamTiles& t, const float* pat,
                               const int32_t* idxmap, const float* gin, float* out, hipStream_t stream, bool binned,
-                              TvamRecWriter writer, TvamPerRay per_ray, const char* what) {
+                              TvamRecWriter writer, TvamPerRay per_ray, const char* what, int writer_slots = 1) {
     hipError_t e = hipErrorNotSupported;
     if (mode == TVAM_MODE_FWD) p->bins.acc_float = tvam_knob("TVAM_BIN_FLOAT", 0);
     if (binned)
-        e = tvam_scatter_binned(mode, k, t, pat, idxmap, gin, out, p->bins, stream, writer);
+        e = tvam_scatter_binned(mode, k, t, pat, idxmap, gin, out, p->bins, stream, writer, writer_slots);
     else
         for (auto& v : p->bins.st) v = 0;  // nothing binned
     if (e == hipErrorNotSupported) e = per_ray(mode, k, t, pat, idxmap, gin, out, nullptr, stream);
@@ -283,6 +283,10 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
     if ((rc = bind_active(p, kc, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
     if (p->general) {
         TvamTiles t = call_tiles(p, spp, seed);
+        if (p->dbl)  // two medium segments per ray: two record slots per path
+            return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream, tvam_cone_binned(p),
+                                      tvam_double_write_records, tvam_launch_double_rays,
+                                      "double-vial forward launch", 2);
         if (p->cone)
             return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream, tvam_cone_binned(p),
                                       tvam_cone_write_records, tvam_launch_cone_rays, "projector-ray forward launch");
@@ -414,8 +418,9 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     if (p->general) {
         if (p->empty) return 0;
         TvamTiles t = call_tiles(p, spp, seed);
-        e = p->cone ? tvam_launch_cone_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
-                    : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
+        e = p->dbl    ? tvam_launch_double_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+            : p->cone ? tvam_launch_cone_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+                      : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
         return e == hipSuccess ? 0 : tvam_hip_fail(e, "path adjoint launch");
     }
     if (p->surface) {
@@ -446,14 +451,32 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     return 0;
 }
 
-// The rays of a call (tvam_cone.hip's ray generation serves every projector kind).
+// The rays of a call (tvam_cone.hip's ray generation serves every projector kind); `segs`: both
+// medium segments of a 'double_cylindrical' plan instead (tvam_plan_segments).
+static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                       float* rays, float* segs, void* stream_);
+
 extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                               uint32_t seed, float* rays, void* stream_) {
     if (!p || (!rays && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     const tvam_desc& d = p->desc;
-    if ((d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM) || d.albedo != 0.0f ||
-        d.n_occluder_tris > 0)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched and 'custom' vial plans without scattering or occluders only");
+    if ((d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM &&
+         d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL) ||
+        d.albedo != 0.0f || d.n_occluder_tris > 0)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched, 'custom' and 'double_cylindrical' vial plans without scattering or occluders only");
+    return export_rays(p, active_pixels, n_active, spp, seed, rays, nullptr, stream_);
+}
+
+extern "C" int tvam_plan_segments(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
+                                  uint32_t seed, float* segs, void* stream_) {
+    if (!p || (!segs && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (!p->dbl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: 'double_cylindrical' vial plans only");
+    if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_segments: segs must be 16-byte aligned");
+    return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_);
+}
+
+static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                       float* rays, float* segs, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     TvamConsts k;
     int rc = call_setup(p, n_active, active_pixels, spp, k);
@@ -463,7 +486,8 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
     const int32_t* idxmap = nullptr;
     if ((rc = bind_active(p, k, nullptr, active_pixels, n_active, stream, nullptr, &idxmap))) return rc;
     TvamTiles t = call_tiles(p, spp, seed);
-    e = tvam_launch_cone_export(k, t, idxmap, rays, stream);
+    e = p->dbl ? tvam_launch_double_export(k, t, idxmap, rays, segs, stream)
+               : tvam_launch_cone_export(k, t, idxmap, rays, stream);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "ray export launch");
 }
 
@@ -478,8 +502,9 @@ extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint
     if (e != hipSuccess) return tvam_hip_fail(e, "hipMemset");
     TvamTiles t = call_tiles(p, spp, seed);
     if (p->general) {
-        e = p->cone ? tvam_launch_cone_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
-                    : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
+        e = p->dbl    ? tvam_launch_double_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
+            : p->cone ? tvam_launch_cone_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
+                      : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
     } else if (p->surface) {
         e = tvam_launch_surface_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, nullptr, p->counter.get(),
                                       nullptr);
@@ -508,6 +533,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
         return tvam_fail(TVAM_ERR_INVALID, "null argument");
     if (p->mesh)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'custom' vial with filter_radon is not implemented on the GPU path");
+    if (p->dbl)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_radon is not implemented on the GPU path");
     if (p->cone)  // the Radon path is a planar ray (tvam_radon_ray)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "the 'telecentric' / 'lens' projectors with filter_radon are not implemented on the GPU path");
     TvamConsts k;
@@ -534,6 +561,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
 extern "C" int tvam_corner(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, float dist, float radius,
                            float* keep, float* hits, void* stream_) {
     if (!p) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: null plan");
+    if (p->dbl)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_corner is not implemented on the GPU path");
     if (!keep) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: null keep");
     if (!(radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: radius must be >= 0");
     if (!std::isfinite(dist)) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: dist must be finite");

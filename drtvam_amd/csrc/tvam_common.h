@@ -51,6 +51,13 @@ struct TvamMesh {
     int32_t lds_bytes;    // > 0: the three tables fit the kernels' LDS staging budget (their bytes)
 };
 
+// A 'double_cylindrical' vial's four tubes (tvam_double.h), outermost first: radius and
+// eta = IOR inside the tube / IOR outside it (air, outer glass, medium, inner glass, core).
+struct TvamDouble {
+    float r0, r1, r2, r3;
+    float eta0, eta1, eta2, eta3;
+};
+
 struct TvamConsts {
     // film / sensor (sensor.py:14-19, film.py:9-14)
     float bmin[3], bmax[3], h[3];
@@ -97,8 +104,14 @@ struct TvamConsts {
     float ap_r;           // 'aperture_radius'
     float focus;          // 'focus_distance'
     float dist;           // 'distance' (camera-space z = 0: the aperture plane)
-    TvamMesh mesh;        // 'custom' vial (vial_type 3), else zeroes
+    // the vial's own tables, one vial at a time: sharing the bytes keeps the kernels' argument
+    // block, and with it the register allocation of every kernel, what it was without the second
+    union {
+        TvamMesh mesh;    // 'custom' vial (vial_type 3), else zeroes
+        TvamDouble dbl;   // 'double_cylindrical' vial (vial_type 4)
+    };
 };
+static_assert(sizeof(TvamDouble) <= sizeof(TvamMesh), "TvamConsts: the vial union must keep TvamMesh's size");
 
 // --------------------------------------------------------------------------
 // Sampler: TEA-scrambled PCG32 (Mitsuba 'independent' sampler, restated)

@@ -38,76 +38,6 @@ __device__ __forceinline__ bool cn_ray(const TvamConsts& k, const TvamTiles& tp,
 // the workgroup's LDS copy of the meshes (CN_MESH_LDS launches pass cn_mesh_lds_bytes of dynamic LDS)
 extern __shared__ float4 cn_mesh_lds[];
 
-// The segment's DDA (sensor.py:327-438), stepped like the oracle's or_dda op for op in fp32: the
-// box clip, start / end voxel, dtmax / tstep per axis, then per visit dt = min(dtmax, remaining),
-// dtmax -= dt (an axis at its crossing restarts from tstep), so a ray visits exactly the oracle's
-// voxels (sc_dda's closed-form crossing times fmaf(n, ts, dtm0) can split a near-tie the other
-// way).  The visit weight e^{-st t} (1 - e^{-st dt}) without cancellation (tvam_omexp).  FWD adds
-// em * weight into dose, ADJ returns sum weight * grad * inv_vol, COUNT counts visits.
-template <int MODE>
-__device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], const float d[3], float maxt, float em,
-                                        float* __restrict__ dose, const float* __restrict__ gin, uint64_t& nvis) {
-    float lo[3], hi[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float tb0 = (k.bmin[a] - o[a]) / d[a];
-        const float tb1 = (k.bmax[a] - o[a]) / d[a];
-        lo[a] = fminf(tb0, tb1);
-        hi[a] = fmaxf(tb0, tb1);
-    }
-    const float t_start = fmaxf(fmaxf(fmaxf(fmaxf(lo[0], lo[1]), lo[2]), 0.0f), 0.0f);
-    const float t_end = fminf(fminf(fminf(hi[0], hi[1]), hi[2]), maxt);
-    if (!(isfinite(t_start) && isfinite(t_end) && t_start < t_end)) return 0.0f;
-    // axes in scalars (dynamically indexed arrays would be promoted to scratch)
-    int cur[3], endv[3], step[3];
-    float dtm[3], ts[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float gs = fmaf(d[a], t_start, o[a]), ge = fmaf(d[a], t_end, o[a]);
-        step[a] = d[a] > 0.0f ? 1 : -1;
-        int sv = (int)((gs - k.bmin[a]) / k.h[a]);
-        int ev = (int)((ge - k.bmin[a]) / k.h[a]);
-        sv = sv < 0 ? 0 : (sv > k.res[a] - 1 ? k.res[a] - 1 : sv);
-        ev = ev < 0 ? 0 : (ev > k.res[a] - 1 ? k.res[a] - 1 : ev);
-        cur[a] = sv;
-        endv[a] = ev;
-        float next = k.bmin[a] + (float)(sv + step[a]) * k.h[a];
-        if (d[a] < 0.0f) next = next + k.h[a];
-        const bool valid = fabsf(d[a]) > 1e-8f;
-        float dt0 = valid ? (next - gs) / d[a] : TVAM_INF;
-        if (dt0 < 0.0f) dt0 = TVAM_INF;  // sensor.py:358: the axis never steps
-        dtm[a] = dt0;
-        ts[a] = valid ? (k.h[a] / d[a]) * (float)step[a] : TVAM_INF;
-    }
-    const int64_t sy = k.res[0], sz = (int64_t)k.res[0] * k.res[1];
-    float t = t_start, remaining = t_end - t_start, acc = 0.0f;
-    // a ray steps at most res - 1 times per axis (the guard only bounds the loop)
-    const int nmax = k.res[0] + k.res[1] + k.res[2] + 1;
-    for (int it = 0; it < nmax; ++it) {
-        const float dt = fminf(fminf(fminf(dtm[0], dtm[1]), dtm[2]), remaining);
-        remaining = remaining - dt;
-        const int64_t idx = cur[0] + cur[1] * sy + cur[2] * sz;
-        if (MODE != TVAM_MODE_COUNT) {
-            const float c = sc_exp2(k.nsig2 * t) * tvam_omexp(k.sig_t * fmaxf(dt, 0.0f));
-            if (MODE == TVAM_MODE_FWD) atomicAdd(&dose[idx], em * c);
-            else acc = fmaf(c, gin[idx] * k.inv_vol, acc);
-        }
-        ++nvis;
-        const bool alive = (cur[0] != endv[0] || cur[1] != endv[1] || cur[2] != endv[2]) && remaining > 1e-6f;
-        if (!alive) break;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const bool m = dtm[a] == dt;
-            dtm[a] = m ? ts[a] : dtm[a] - dt;
-            cur[a] += m ? step[a] : 0;
-        }
-        if (cur[0] < 0 || cur[1] < 0 || cur[2] < 0 || cur[0] >= k.res[0] || cur[1] >= k.res[1] || cur[2] >= k.res[2])
-            break;
-        t = t + dt;
-    }
-    return acc;
-}
-
 template <int MODE, int MESH>
 __global__ __launch_bounds__(256) void tvam_cone_kernel(TvamConsts k, TvamTiles tp, const float* __restrict__ pat,
                                                         const int32_t* __restrict__ idxmap,

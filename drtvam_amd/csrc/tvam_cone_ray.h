@@ -1,7 +1,8 @@
 // tvam_cone_ray.h -- ray generation of the telecentric / lens projectors (projector.py:199-296),
 // shared by tvam_cone.hip (forward, adjoint, export) and tvam_corner.hip (the 'filter_corner'
 // first-hit pass): the sampler draws, get_ray, CircularMotion's to_world and the medium segment
-// behind the index-matched vial, or behind the mesh interfaces of a 'custom' vial (device only).
+// behind the index-matched vial, or behind the mesh interfaces of a 'custom' vial, and the per-ray
+// DDA of a 3-D segment (cn_dda), which tvam_cone.hip and tvam_double.hip march (device only).
 #pragma once
 #include "tvam_mesh.h"
 #include "tvam_path.h"
@@ -95,8 +96,9 @@ __device__ __forceinline__ bool cn_segment(const TvamConsts& k, ConeRay& r) {
 // The ray of shard angle `al`, crop pixel (colc, rowc), drawn from sampler stream `stream` of seed
 // tp.seed, and its medium segment.  Returns whether it deposits.  The collimated projector takes
 // tvam_ray_world / tvam_segment_im (the ray records' own expressions), so that the export of such
-// a plan is the oracle's ray bit for bit.
-template <int MESH = CN_NO_MESH>
+// a plan is the oracle's ray bit for bit.  RAY_ONLY: the world-space projector ray (r.o, r.d) alone,
+// for a caller that traces the vial itself (tvam_double.hip).
+template <int MESH = CN_NO_MESH, bool RAY_ONLY = false>
 __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& tp, int al, int colc, int rowc,
                                           uint64_t stream, ConeRay& r, const TvamMeshView* mesh = nullptr) {
     TvamPcg rng;
@@ -107,6 +109,7 @@ __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& 
     if (k.proj_type == TVAM_PROJECTOR_COLLIMATED) {
         tvam_ray_world(k, c, sn, xc, yc, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1]);
         r.d[2] = 0.0f;
+        if (RAY_ONLY) return true;
         if (MESH != CN_NO_MESH) return cn_segment_mesh(k, *mesh, r);
         r.o2[2] = r.o[2];
         return tvam_segment_im(k, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.o2[0], r.o2[1], r.maxt);
@@ -144,8 +147,85 @@ __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& 
     r.d[0] = sn * vx - c * vz;
     r.d[1] = -sn * vz - c * vx;
     r.d[2] = vy;
+    if (RAY_ONLY) return true;
     if (MESH != CN_NO_MESH) return cn_segment_mesh(k, *mesh, r);
     return cn_segment(k, r);
+}
+
+// The projector ray alone.
+__device__ __forceinline__ void cn_projector_ray(const TvamConsts& k, const TvamTiles& tp, int al, int colc, int rowc,
+                                                 uint64_t stream, ConeRay& r) {
+    (void)cn_ray_at<CN_NO_MESH, true>(k, tp, al, colc, rowc, stream, r);
+}
+
+// The segment's DDA (sensor.py:327-438), stepped like the oracle's or_dda op for op in fp32: the
+// box clip, start / end voxel, dtmax / tstep per axis, then per visit dt = min(dtmax, remaining),
+// dtmax -= dt (an axis at its crossing restarts from tstep), so a ray visits exactly the oracle's
+// voxels (sc_dda's closed-form crossing times fmaf(n, ts, dtm0) can split a near-tie the other
+// way).  The visit weight e^{-st t} (1 - e^{-st dt}) without cancellation (tvam_omexp).  FWD adds
+// em * weight into dose, ADJ returns sum weight * grad * inv_vol, COUNT counts visits.
+template <int MODE>
+__device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], const float d[3], float maxt, float em,
+                                        float* __restrict__ dose, const float* __restrict__ gin, uint64_t& nvis) {
+    float lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float tb0 = (k.bmin[a] - o[a]) / d[a];
+        const float tb1 = (k.bmax[a] - o[a]) / d[a];
+        lo[a] = fminf(tb0, tb1);
+        hi[a] = fmaxf(tb0, tb1);
+    }
+    const float t_start = fmaxf(fmaxf(fmaxf(fmaxf(lo[0], lo[1]), lo[2]), 0.0f), 0.0f);
+    const float t_end = fminf(fminf(fminf(hi[0], hi[1]), hi[2]), maxt);
+    if (!(isfinite(t_start) && isfinite(t_end) && t_start < t_end)) return 0.0f;
+    // axes in scalars (dynamically indexed arrays would be promoted to scratch)
+    int cur[3], endv[3], step[3];
+    float dtm[3], ts[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float gs = fmaf(d[a], t_start, o[a]), ge = fmaf(d[a], t_end, o[a]);
+        step[a] = d[a] > 0.0f ? 1 : -1;
+        int sv = (int)((gs - k.bmin[a]) / k.h[a]);
+        int ev = (int)((ge - k.bmin[a]) / k.h[a]);
+        sv = sv < 0 ? 0 : (sv > k.res[a] - 1 ? k.res[a] - 1 : sv);
+        ev = ev < 0 ? 0 : (ev > k.res[a] - 1 ? k.res[a] - 1 : ev);
+        cur[a] = sv;
+        endv[a] = ev;
+        float next = k.bmin[a] + (float)(sv + step[a]) * k.h[a];
+        if (d[a] < 0.0f) next = next + k.h[a];
+        const bool valid = fabsf(d[a]) > 1e-8f;
+        float dt0 = valid ? (next - gs) / d[a] : TVAM_INF;
+        if (dt0 < 0.0f) dt0 = TVAM_INF;  // sensor.py:358: the axis never steps
+        dtm[a] = dt0;
+        ts[a] = valid ? (k.h[a] / d[a]) * (float)step[a] : TVAM_INF;
+    }
+    const int64_t sy = k.res[0], sz = (int64_t)k.res[0] * k.res[1];
+    float t = t_start, remaining = t_end - t_start, acc = 0.0f;
+    // a ray steps at most res - 1 times per axis (the guard only bounds the loop)
+    const int nmax = k.res[0] + k.res[1] + k.res[2] + 1;
+    for (int it = 0; it < nmax; ++it) {
+        const float dt = fminf(fminf(fminf(dtm[0], dtm[1]), dtm[2]), remaining);
+        remaining = remaining - dt;
+        const int64_t idx = cur[0] + cur[1] * sy + cur[2] * sz;
+        if (MODE != TVAM_MODE_COUNT) {
+            const float c = sc_exp2(k.nsig2 * t) * tvam_omexp(k.sig_t * fmaxf(dt, 0.0f));
+            if (MODE == TVAM_MODE_FWD) atomicAdd(&dose[idx], em * c);
+            else acc = fmaf(c, gin[idx] * k.inv_vol, acc);
+        }
+        ++nvis;
+        const bool alive = (cur[0] != endv[0] || cur[1] != endv[1] || cur[2] != endv[2]) && remaining > 1e-6f;
+        if (!alive) break;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const bool m = dtm[a] == dt;
+            dtm[a] = m ? ts[a] : dtm[a] - dt;
+            cur[a] += m ? step[a] : 0;
+        }
+        if (cur[0] < 0 || cur[1] < 0 || cur[2] < 0 || cur[0] >= k.res[0] || cur[1] >= k.res[1] || cur[2] >= k.res[2])
+            break;
+        t = t + dt;
+    }
+    return acc;
 }
 
 }  // namespace

@@ -271,14 +271,15 @@ hipError_t tvam_launch_scatter_paths(int mode, const TvamConsts& k, const TvamTi
 // Forward of the scattered segments through brick bins (chunks of paths; host
 // syncs once per chunk to size the bins).  Returns hipErrorNotSupported when
 // the grid is too large for the packed records (callers then use the atomics).
-// writer: the record writer of another kind of segment (one record per path: slots = 1, forward
-// only; tvam_cone.hip) in place of tvam_scatter_kernel<EMIT>; it fills sb.r / sb.m / sb.wmax of the
-// paths [sb.p0, sb.p1) on `stream` with `grid` workgroups of 256 threads.
+// writer: the record writer of another kind of segment (writer_slots records per path, forward
+// only: one for tvam_cone.hip's first segments, two for tvam_double.hip's) in place of
+// tvam_scatter_kernel<EMIT>; it fills sb.r / sb.m / sb.wmax of the paths [sb.p0, sb.p1) on `stream`
+// with `grid` workgroups of 256 threads (sb.m arrives zeroed: a slot it leaves alone is empty).
 typedef void (*TvamRecWriter)(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
                               const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
-                               hipStream_t stream, TvamRecWriter writer = nullptr);
+                               hipStream_t stream, TvamRecWriter writer = nullptr, int writer_slots = 1);
 // the scratch back to its initial state: its event and pinned word here, the device memory with its owners
 void tvam_bin_scratch_free(TvamBinScratch& s);
 
@@ -308,6 +309,17 @@ void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const floa
                              const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
 hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
                                    hipStream_t stream);
+// 'double_cylindrical' vial (tvam_double.hip): every ray traced through the four tubes, at most two
+// medium segments per ray.  The per-ray kernels, the brick-bin record writer (two slots per path)
+// and the export of the rays (16 floats per ray, may be null) and of both segments ([2][8] floats
+// per ray, may be null).
+hipError_t tvam_launch_double_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                                   const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
+                                   hipStream_t stream);
+void tvam_double_write_records(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
+                               const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
+hipError_t tvam_launch_double_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
+                                     float* segs, hipStream_t stream);
 hipError_t tvam_launch_scale_volumes(int64_t n, const float* vols, float* dose, hipStream_t stream);
 // compute_volume (sensor.py:47-110): volumes [res z][y][x][2]
 hipError_t tvam_launch_volumes(const TvamConsts& k, uint32_t sample_count, float* volumes, hipStream_t stream);

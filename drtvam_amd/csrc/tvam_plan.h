@@ -43,6 +43,7 @@ struct tvam_plan {
     bool mesh = false;       // 'custom' vial: mesh interfaces traced per ray (tvam_mesh.h); implies cone
     const float* vols = nullptr;  // caller's compute_volume() output (tvam_plan_set_volumes)
     TvamDevBuf<float> tgt, occ;   // target mesh (surface-aware films) and occluder triangles
+    bool dbl = false;        // 'double_cylindrical' vial: four tubes traced per ray, two segments (tvam_double.h); implies cone
     TvamDevBuf<float4> mesh_nodes;  // 'custom' vial: the hierarchy over both meshes (TvamMesh)
     TvamDevBuf<float> mesh_tris;
     TvamDevBuf<int32_t> mesh_ids;
@@ -102,7 +103,8 @@ struct tvam_plan {
     // nothing gives nullptr.  (pl.chord and the visit lists' pl.adjl_* are set by their builders.)
     void bind() {
         k.tgt = tgt.get(), k.occ = occ.get();
-        k.mesh.nodes = mesh_nodes.get(), k.mesh.tris = mesh_tris.get(), k.mesh.ids = mesh_ids.get();
+        if (!dbl)  // (k.dbl shares k.mesh's bytes)
+            k.mesh.nodes = mesh_nodes.get(), k.mesh.tris = mesh_tris.get(), k.mesh.ids = mesh_ids.get();
         tiles.cs = cs.get(), tiles.ang = ang.get();
         tiles.slice_off = slice_off.get(), tiles.slice_rows = slice_rows.get();
         tiles.slots = slots.get(), tiles.slot_off = slot_off.get();

@@ -106,6 +106,30 @@ static int validate(const tvam_desc& d) {
         if (d.rr_depth < 2) return no("rr_depth < 2 (Russian roulette before the medium segment)");
         if (!(d.vial_ior > 0.0f && d.medium_ior > 0.0f))
             return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs positive IORs");
+    } else if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) {
+        // two nested glass tubes (tvam_plan_create_double): every ray is traced in 3-D through the
+        // four interfaces and runs the per-ray kernels of tvam_double.hip, whose limits these are
+        auto no = [&](const char* what) {
+            return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string("a 'double_cylindrical' vial with ") + what +
+                                                  " is not implemented on the GPU path");
+        };
+        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
+            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
+            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
+        }
+        if (d.n_occluder_tris > 0) return no("occluders");
+        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
+        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
+        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
+        if (d.film_channels == 2) return no("a surface-aware film");
+        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
+        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
+        // the last deposit is at loop iteration min(max_depth - 1, 6); Russian roulette acts at
+        // iterations > rr_depth (volume.py:182-185)
+        if (d.rr_depth < std::min(d.max_depth, 7) - 1)
+            return no("rr_depth < min(max_depth, 7) - 1 (Russian roulette on or before a deposit)");
+        if (!(d.vial_height > 0.0f))
+            return tvam_fail(TVAM_ERR_INVALID, "a 'double_cylindrical' vial needs a positive height");
     } else if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
         // 3-D projector rays (tvam_cone.hip): index-matched vial, absorbing medium, 'dda' sensor,
         // one-channel film, the whole film
@@ -137,8 +161,9 @@ static int validate(const tvam_desc& d) {
         (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "sample_time and the ratio / delta sensors need a film without slabs");
     if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CYLINDRICAL &&
-        d.vial_type != TVAM_VIAL_SQUARE && d.vial_type != TVAM_VIAL_CUSTOM)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'index_matched', 'cylindrical', 'square' and 'custom' containers are implemented on the GPU path");
+        d.vial_type != TVAM_VIAL_SQUARE && d.vial_type != TVAM_VIAL_CUSTOM &&
+        d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'index_matched', 'cylindrical', 'square', 'custom' and 'double_cylindrical' containers are implemented on the GPU path");
     // transmission_only = False lets the reference sample reflection as well as refraction at every
     // dielectric interface after the first (volume.py:235-243, radon.py:87-95); the kernels only
     // refract.  An index-matched vial has no such interface.
@@ -166,7 +191,7 @@ static int validate(const tvam_desc& d) {
     }
     // the medium segment is path vertex 1 (index matched) or 2 (behind two glass
     // surfaces); Russian roulette starts at depth > rr_depth (volume.py:182-185)
-    if (d.rr_depth < (d.vial_type == TVAM_VIAL_INDEX_MATCHED ? 1 : 2))
+    if (d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL && d.rr_depth < (d.vial_type == TVAM_VIAL_INDEX_MATCHED ? 1 : 2))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "Russian roulette before the medium segment (rr_depth too small) is not implemented");
     if (d.n_patterns <= 0 || d.res_x <= 0 || d.res_y <= 0) return tvam_fail(TVAM_ERR_INVALID, "projector resolution and n_patterns must be positive");
     if (d.crop_x <= 0 || d.crop_y <= 0 || d.crop_x > d.res_x || d.crop_y > d.res_y)
@@ -178,10 +203,12 @@ static int validate(const tvam_desc& d) {
         if (d.film_res[a] <= 0) return tvam_fail(TVAM_ERR_INVALID, "film resolution must be positive");
         if (!(d.bbox_max[a] > d.bbox_min[a])) return tvam_fail(TVAM_ERR_INVALID, "sensor bounding box is empty");
     }
-    // (a 'custom' vial's surfaces are its meshes: vial_r, vial_r_ext and vial_height are unused)
-    if (d.vial_type != TVAM_VIAL_CUSTOM && !(d.vial_r > 0.0f))
+    // (a 'custom' vial's surfaces are its meshes: vial_r, vial_r_ext and vial_height are unused; a
+    // 'double_cylindrical' vial's radii are tvam_double_vial's)
+    const bool own_surfaces = d.vial_type == TVAM_VIAL_CUSTOM || d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL;
+    if (!own_surfaces && !(d.vial_r > 0.0f))
         return tvam_fail(TVAM_ERR_INVALID, "vial radius must be positive");
-    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM &&
+    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !own_surfaces &&
         !(d.vial_r_ext > d.vial_r && d.vial_ior > 0.0f && d.medium_ior > 0.0f && d.vial_height > 0.0f))
         return tvam_fail(TVAM_ERR_INVALID, "glass vial: need r_ext > r_int > 0 (w_ext > w_int) and positive IORs");
     {
@@ -1225,14 +1252,31 @@ static int upload_vial_meshes(tvam_plan* p, const float* outer, int32_t n_outer,
 }
 
 static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
-                       int device, tvam_plan** out);
+                       const tvam_double_vial* dbl, int device, tvam_plan** out);
+// tvam_double.hip
+int tvam_double_validate(const tvam_double_vial* v, float medium_ior);
+TvamDouble tvam_double_consts(const tvam_double_vial& v, float medium_ior);
 
 extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** out) {
     if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     *out = nullptr;
     if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_CUSTOM)
         return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs its meshes: create the plan with tvam_plan_create_mesh");
-    return plan_create(*desc, nullptr, 0, nullptr, 0, device, out);
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL)
+        return tvam_fail(TVAM_ERR_INVALID, "a 'double_cylindrical' vial needs its radii and IORs: create the plan with tvam_plan_create_double");
+    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out);
+}
+
+extern "C" int tvam_plan_create_double(const tvam_desc* desc, const tvam_double_vial* vial, int device,
+                                       tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_double: vial_type must be TVAM_VIAL_DOUBLE_CYLINDRICAL");
+    int rc = validate(*desc);
+    if (rc) return rc;
+    if ((rc = tvam_double_validate(vial, desc->medium_ior))) return rc;
+    return plan_create(*desc, nullptr, 0, nullptr, 0, vial, device, out);
 }
 
 extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_t n_outer,
@@ -1247,11 +1291,16 @@ extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_t
         return rc;
     if ((int64_t)n_outer + n_inner >= (1 << 27))
         return tvam_fail(TVAM_ERR_TOO_LARGE, "the vial meshes have too many triangles");
-    return plan_create(*desc, outer_tris, n_outer, inner_tris, n_inner, device, out);
+    return plan_create(*desc, outer_tris, n_outer, inner_tris, n_inner, nullptr, device, out);
 }
 
-static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
-                       int device, tvam_plan** out) {
+static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_outer, const float* inner,
+                       int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out) {
+    tvam_desc d = d_in;
+    if (dbl) {  // the host tables (tiles, slots) are sized by the medium's tube and the outermost one
+        d.vial_r = dbl->r_int_outer;
+        d.vial_r_ext = dbl->r_ext_outer;
+    }
     int rc = validate(d);
     if (rc) return rc;
     int a0 = d.angle_begin, a1 = d.angle_end < 0 ? d.n_patterns : d.angle_end;
@@ -1274,7 +1323,12 @@ static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, 
     p->surface = d.film_channels == 2;
     p->mesh = d.vial_type == TVAM_VIAL_CUSTOM;
     if (p->mesh) p->empty = d.max_depth < 3;  // two glass surfaces + the medium segment, like the glass vials
-    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh;
+    p->dbl = dbl != nullptr;
+    if (p->dbl) {
+        p->empty = d.max_depth < 3;  // the first deposit is at loop iteration 2
+        p->k.dbl = tvam_double_consts(*dbl, d.medium_ior);
+    }
+    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh || p->dbl;
     p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
     if ((rc = upload_meshes(p.get())) || (rc = tile_geometry(p.get()))) return rc;
     if (p->mesh && (rc = upload_vial_meshes(p.get(), outer, n_outer, inner, n_inner))) return rc;
@@ -1361,6 +1415,8 @@ extern "C" int tvam_row_slices(const tvam_desc* desc, int32_t* slice_of_row) {
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: the 'telecentric' / 'lens' projectors' rays leave their slice (no film slabs)");
     if (d.vial_type == TVAM_VIAL_CUSTOM)  // refracted at tilted faces, they leave it too
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: a 'custom' vial's rays leave their slice (no film slabs)");
+    if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL)  // per-ray 3-D kernels: no film slabs
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: a 'double_cylindrical' vial runs the 3-D per-ray path (no film slabs)");
     const TvamConsts k = make_consts(d, 0, d.n_patterns);
     for (int r = 0; r < d.crop_y; ++r) {
         float xc, yc;

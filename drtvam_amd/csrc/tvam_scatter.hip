@@ -1302,7 +1302,7 @@ void tvam_bin_scratch_free(TvamBinScratch& s) {
 
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
-                               hipStream_t stream, TvamRecWriter writer) {
+                               hipStream_t stream, TvamRecWriter writer, int writer_slots) {
     for (int i = 0; i < 5; ++i) s.st[i] = 0;  // stats of this call, also when it bins nothing
     // an earlier call's count check, if its copy has landed: a slot whose brick walk disagreed with
     // the writer's closed-form count (never, by construction) may have dropped entries -- fail loudly
@@ -1311,8 +1311,8 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
         if (*s.bad_host) return hipErrorIllegalState;
     }
     const int nsurf = k.vial_type == 0 ? 1 : 2;
-    // later medium segments per path; a record writer of first segments writes one per path
-    const int slots = writer ? 1 : k.max_depth - nsurf - 1;
+    // later medium segments per path; a record writer writes its own count per path
+    const int slots = writer ? writer_slots : k.max_depth - nsurf - 1;
     if (slots <= 0) return hipSuccess;
     if (writer && mode != TVAM_MODE_FWD) return hipErrorNotSupported;
     if (k.res[0] > 2048 || k.res[1] > 2048 || k.res[2] > 1024) return hipErrorNotSupported;

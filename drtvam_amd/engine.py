@@ -58,6 +58,11 @@ class Projection:
                     0 if outer is None else int(outer.shape[0]),
                     None if inner is None or not inner.size else inner.ctypes.data,
                     0 if inner is None else int(inner.shape[0]), self.device.index, ctypes.byref(plan)))
+            elif self.desc.vial_type == _abi.VIAL_DOUBLE_CYLINDRICAL:  # radii and IORs beside the struct
+                vial = getattr(self.desc, "_double_vial", None)
+                _abi.check(self.lib.tvam_plan_create_double(
+                    ctypes.byref(self.desc), None if vial is None else ctypes.byref(vial), self.device.index,
+                    ctypes.byref(plan)))
             else:
                 _abi.check(self.lib.tvam_plan_create(ctypes.byref(self.desc), self.device.index, ctypes.byref(plan)))
         self._plan = plan
@@ -230,8 +235,9 @@ class Projection:
         """The projector rays of a call (tvam_plan_rays), [n_active * spp, 16] float32 in sampler-stream
         order (row = active entry * spp + sample): o[0:3], d[3:6], hit [6], o2[7:10], maxt [10],
         d2[11:14], weight [14] (the whole per-ray weight), 0.  The diagnostic counterpart of the
-        oracle's ray(); index-matched plans with a non-scattering medium, and 'custom' vial plans
-        (d2: the refracted direction; the weight carries the interfaces' transmission)."""
+        oracle's ray(); index-matched plans with a non-scattering medium, and 'custom' and
+        'double_cylindrical' vial plans (d2: the refracted direction; the weight carries the
+        interfaces' transmission; double_cylindrical: the first of the two segments, see segments())."""
         if active_pixels is not None:
             self._check_pixels(active_pixels)
             n_active = int(active_pixels.numel())
@@ -247,9 +253,31 @@ class Projection:
                 seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
         return out
 
+    def segments(self, n_active: Optional[int] = None, active_pixels: Optional[torch.Tensor] = None, spp: int = 1,
+                 seed: int = 0) -> torch.Tensor:
+        """Both medium segments of a call's rays behind a 'double_cylindrical' vial (tvam_plan_segments),
+        [n_active * spp, 2, 8] float32 in sampler-stream order: o2[0:3], maxt [3], d2[4:7], weight [7]
+        (the whole per-ray weight times the attenuation the segment starts with); a slot without a
+        segment is all zeros."""
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+            n_active = int(active_pixels.numel())
+        elif n_active is None:
+            a0, a1 = self.desc.angle_begin, (self.desc.angle_end if self.desc.angle_end >= 0 else self.desc.n_patterns)
+            n_active = (a1 - a0) * self.desc.crop_y * self.desc.crop_x
+        if self.desc.regular_sampling:
+            spp = 1  # common.py:49-51
+        out = torch.zeros((int(n_active) * int(spp), 2, 8), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_plan_segments(
+                self._plan, None if active_pixels is None else active_pixels.data_ptr(), int(n_active), int(spp),
+                seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
     @property
     def cone(self) -> bool:
-        """True for the 3-D per-ray path: a telecentric / lens projector, or a 'custom' vial."""
+        """True for the 3-D per-ray path: a telecentric / lens projector, or a 'custom' or
+        'double_cylindrical' vial."""
         return bool(self.lib.tvam_plan_path(self._plan) & 4)
 
     @property

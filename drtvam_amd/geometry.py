@@ -223,8 +223,36 @@ class DoubleCylindricalVial(Container):
         self.vial_ior_outer = params['ior_outer']
         self.inside_inner_ior = params['ior_inside_inner']
 
+    def _tube(self, radius, bsdf, **medium):
+        return {'type': 'cylinder', 'p0': [0., 0., -0.5 * self.height], 'p1': [0., 0., 0.5 * self.height],
+                'radius': radius, 'bsdf': {'type': 'dielectric', **bsdf}, **medium}
+
     def to_dict(self):
-        return {'printing_medium': self.medium_dict()}
+        ref = {'type': 'ref', 'id': 'printing_medium'}
+        return {
+            'printing_medium': self.medium_dict(),
+            'outer_vial': self._tube(self.r_ext_outer, {'int_ior': self.vial_ior_outer}),
+            'outer_vial_interior': self._tube(self.r_int_outer,
+                                              {'ext_ior': self.vial_ior_outer, 'int_ior': self.medium_ior}, interior=ref),
+            'inner_vial': self._tube(self.r_ext_inner, {'ext_ior': self.medium_ior, 'int_ior': self.vial_ior_inner},
+                                     exterior=ref),
+            'inner_vial_interior': self._tube(self.r_int_inner,
+                                              {'ext_ior': self.vial_ior_inner, 'int_ior': self.inside_inner_ior}),
+        }
+
+    def fill_desc(self, desc):
+        """The medium, the height and vial_type in the descriptor; the radii and the glass / core IORs
+        beside it (set_double_vial), handed to tvam_plan_create_double."""
+        if self.occlusions:
+            raise NotImplementedError("a 'double_cylindrical' vial with occluders is not implemented on the GPU path")
+        self._fill_medium(desc)
+        desc.vial_type = _abi.VIAL_DOUBLE_CYLINDRICAL
+        desc.vial_height = float(self.height)
+        desc.vial_r = float(self.r_int_outer)      # (unused by the kernels: the medium's tube
+        desc.vial_r_ext = float(self.r_ext_outer)  # and the outermost one, for readers of the struct)
+        desc.set_double_vial(self.r_ext_outer, self.r_int_outer, self.r_ext_inner, self.r_int_inner,
+                             lookup_ior(self.vial_ior_outer), lookup_ior(self.vial_ior_inner),
+                             lookup_ior(self.inside_inner_ior))
 
 
 geometries = {

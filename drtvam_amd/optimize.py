@@ -531,7 +531,8 @@ class TvamProblem(ShardedLoop):
         full_desc = VolumeIntegrator(base).desc(self.scene, self.sensor)
         self.res_z = int(full_desc.film_res[2])
         custom = int(full_desc.vial_type) == 3  # _abi.VIAL_CUSTOM: mesh interfaces, 3-D per-ray path
-        if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0 or custom):
+        double = int(full_desc.vial_type) == 4  # _abi.VIAL_DOUBLE_CYLINDRICAL: nested tubes, 3-D per-ray path
+        if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0 or custom or double):
             # every path marched, as the reference marches every active pixel (projector.py:66-70,
             # common.py:81-82): a scattering scene's paths (and a telecentric / lens projector's
             # binned first segments) then do not depend on the pattern, and
@@ -555,7 +556,14 @@ class TvamProblem(ShardedLoop):
                              "faces and leave their slice (use shard 'angle')")
         if custom and config.get('filter_radon', False) and filter_pixels:
             raise NotImplementedError("filter_radon with a 'custom' vial is not implemented on the GPU path")
-        cone = int(full_desc.projector_type) != 0 or custom
+        if double and shard == 'slab':
+            raise ValueError("z-slab sharding is not implemented for a 'double_cylindrical' vial: it runs the 3-D "
+                             "per-ray path (use shard 'angle')")
+        if double and config.get('filter_radon', False) and filter_pixels:
+            raise NotImplementedError("filter_radon with a 'double_cylindrical' vial is not implemented on the GPU path")
+        if double and 'filter_corner' in config and filter_pixels:
+            raise NotImplementedError("filter_corner with a 'double_cylindrical' vial is not implemented on the GPU path")
+        cone = int(full_desc.projector_type) != 0 or custom or double
         if cone and shard == 'slab':
             raise ValueError("z-slab sharding needs planar rays: the 'telecentric' and 'lens' projectors' rays "
                              "leave their slice (use shard 'angle')")

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .geometry import CustomVial, CylindricalVial, IndexMatchedVial, Container
+from .geometry import CustomVial, CylindricalVial, DoubleCylindricalVial, IndexMatchedVial, Container
 from .integrators import integrators, VolumeIntegrator
 from .projector import TVAMProjector, emitters
 from .sensor import VolumetricSensor, sensors
@@ -79,6 +79,17 @@ def _container_from_shapes(scene_dict):
                                     'height': float(abs(p1[2] - p0[2])),
                                     'ior': bsdf.get('ext_ior', 1.5),
                                     'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
+        if len(outer) == 3:  # DoubleCylindricalVial.to_dict: four nested dielectric tubes
+            by_r = sorted(outer + [shp], key=lambda v: -v['radius'])
+            if by_r[1] is shp and 'exterior' in by_r[2] and all(v.get('bsdf', {}).get('type') == 'dielectric' for v in by_r):
+                p0, p1 = np.asarray(shp['p0'], float), np.asarray(shp['p1'], float)
+                return DoubleCylindricalVial({
+                    'r_ext_outer': by_r[0]['radius'], 'r_int_outer': by_r[1]['radius'],
+                    'r_ext_inner': by_r[2]['radius'], 'r_int_inner': by_r[3]['radius'],
+                    'height': float(abs(p1[2] - p0[2])), 'ior_outer': bsdf.get('ext_ior', 1.5),
+                    'ior_inner': by_r[2]['bsdf'].get('int_ior', 1.5),
+                    'ior_inside_inner': by_r[3]['bsdf'].get('int_ior', 1.0),
+                    'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
     if shp['type'] == 'ply' and bsdf.get('type') == 'dielectric':  # CustomVial.to_dict: two dielectric meshes
         outer = [v for k, v in shapes.items() if k != name and v['type'] == 'ply'
                  and v.get('bsdf', {}).get('type') == 'dielectric']

@@ -65,6 +65,8 @@ extern "C" {
 #define TVAM_VIAL_SQUARE          2  /* glass cuboids w_ext / w_int (vial_r = w_int/2, vial_r_ext = w_ext/2) */
 #define TVAM_VIAL_CUSTOM          3  /* dielectric triangle meshes (tvam_plan_create_mesh; vial_r, vial_r_ext and
                                         vial_height unused) */
+#define TVAM_VIAL_DOUBLE_CYLINDRICAL 4  /* two nested glass tubes (tvam_plan_create_double; vial_r and vial_r_ext
+                                        unused: the radii are tvam_double_vial's) */
 
 /* medium phase functions (Mitsuba 'isotropic', 'rayleigh', 'hg'; geometry.py:29-39) */
 #define TVAM_PHASE_ISOTROPIC      0
@@ -213,6 +215,57 @@ int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_
  */
 int tvam_mesh_hit(const float* tris, int32_t n, const float* o, const float* d, int64_t n_rays, int32_t use_bvh,
                   float* t, int32_t* tri);
+
+/*
+ * A 'double_cylindrical' vial (geometry.py:222-308): four concentric open tubes around z with
+ * |z| <= vial_height / 2 and outward normals, outermost first.  The printing medium fills the gap
+ * between the outer vial's inside wall (r_int_outer) and the inner vial's outside wall
+ * (r_ext_inner); the core inside r_int_inner holds no resin.  vial_height, medium_ior and sigma_t
+ * are the descriptor's.
+ */
+typedef struct tvam_double_vial {
+    float r_ext_outer;       /* air            | outer glass */
+    float r_int_outer;       /* outer glass    | medium      */
+    float r_ext_inner;       /* medium         | inner glass */
+    float r_int_inner;       /* inner glass    | core        */
+    float ior_outer;         /* outer glass */
+    float ior_inner;         /* inner glass */
+    float ior_inside_inner;  /* the core */
+} tvam_double_vial;
+
+/*
+ * A plan behind a 'double_cylindrical' vial (vial_type = TVAM_VIAL_DOUBLE_CYLINDRICAL).  Every ray
+ * is traced in 3-D through the four dielectric tubes (volume.py:179-272 in transmission-only mode:
+ * nearest hit, Fresnel transmission, spawn offset, medium flag, at most max_depth surfaces) and
+ * deposits along 0, 1 or 2 medium segments: before and, for rays that cross the inner vial, behind
+ * it; the second segment's weight carries e^{-sigma_t t} of the first.  Such a plan runs per-ray
+ * 3-D kernels for all three projectors.  TVAM_ERR_INVALID unless r_ext_outer > r_int_outer >
+ * r_ext_inner > r_int_inner > 0 and all IORs are positive.  TVAM_ERR_UNSUPPORTED, by name:
+ * occluders, albedo > 0, the ratio / delta sensors, a surface-aware film, film slabs,
+ * transmission_only = 0, rr_depth < min(max_depth, 7) - 1 (Russian roulette would act on or before
+ * a deposit).  All of it is checked before any device call.  tvam_plan_create refuses
+ * TVAM_VIAL_DOUBLE_CYLINDRICAL and names this entry.
+ */
+int tvam_plan_create_double(const tvam_desc* desc, const tvam_double_vial* vial, int device, tvam_plan** plan);
+
+/*
+ * The medium segments of a call's rays behind a 'double_cylindrical' vial: segs is a device array
+ * [n_active * spp][2][8] floats in sampler-stream order (row = active entry * spp + sample), each
+ * segment o2[3], maxt, d2[3], weight (the whole per-ray weight of tvam_plan_rays times the
+ * attenuation the segment starts with); a slot without a segment is all zeros.  active_pixels as
+ * in tvam_forward.  TVAM_ERR_UNSUPPORTED on any other plan.  tvam_plan_rays on such a plan gives
+ * the projector ray and the first segment in its own layout.
+ */
+int tvam_plan_segments(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
+                       uint32_t seed, float* segs, void* hip_stream);
+
+/*
+ * The same segments on the host, with the code the kernels run and no GPU touched: n_rays world
+ * rays (o, d: [n_rays][3], host) through `vial`, segs: host [n_rays][2][8] in the layout above with
+ * weight = the attenuation alone.  TVAM_ERR_INVALID for a vial tvam_plan_create_double refuses.
+ */
+int tvam_double_segments(const tvam_double_vial* vial, float medium_ior, float sigma_t, float height,
+                         int32_t max_depth, const float* o, const float* d, int64_t n_rays, float* segs);
 
 /*
  * Forward projection (primal render).  Writes the whole film
@@ -513,9 +566,10 @@ int tvam_plan_adj_chunk(const tvam_plan* plan);
  * it deposits, its medium segment (o2, d2, [0, maxt]) and its whole weight (inv_pdf / n_samples *
  * print_time * sigma_a / sigma_t; multiply by the pattern value and 1 / voxel volume for the dose).
  * active_pixels as in tvam_forward (NULL: the dense crop order).  All three projector kinds on
- * index-matched plans with a non-scattering medium, and on 'custom' vial plans, whose d2 is the
- * refracted direction and whose weight carries the product of the interfaces' transmission
- * weights; TVAM_ERR_UNSUPPORTED otherwise.
+ * index-matched plans with a non-scattering medium, and on 'custom' and 'double_cylindrical' vial
+ * plans, whose d2 is the refracted direction and whose weight carries the product of the
+ * interfaces' transmission weights (double_cylindrical: the first of the two segments, see
+ * tvam_plan_segments); TVAM_ERR_UNSUPPORTED otherwise.
  */
 int tvam_plan_rays(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                    uint32_t seed, float* rays, void* hip_stream);
