@@ -243,6 +243,7 @@ EXPORTS = {
         [_P, _P, _P, ctypes.c_int32, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_float,
          ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P],
     ),
+    "tvam_class_hist": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),
     "tvam_last_error": (ctypes.c_char_p, []),
     "tvam_abi_version": (ctypes.c_int, []),
     "tvam_device_bytes": (ctypes.c_int64, []),

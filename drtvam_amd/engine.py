@@ -471,3 +471,62 @@ def loss_threshold(dose: torch.Tensor, target: torch.Tensor, K: int, tl: float, 
                 int(K), float(tl), float(tu), float(w_object), float(w_void), float(w_limit), float(scale),
                 out.data_ptr(), None if grad is None else grad.data_ptr(), _stream_ptr(dose.device)))
     return out[0]
+
+
+def _check_edges(edges, side: int) -> None:
+    """tvam_class_hist's argument checks, for the torch path (the CUDA path leaves them to the library)."""
+    import numpy as np
+    k = int(edges.size)
+    if not 1 <= k <= 2048:
+        raise ValueError(f"class_hist: 1 <= n_edges <= 2048 (got {k})")
+    if side not in (0, 1):
+        raise ValueError(f"class_hist: side must be 0 or 1 (got {side})")
+    bad = np.flatnonzero(~np.isfinite(edges))
+    if bad.size:
+        raise ValueError(f"class_hist: edge {int(bad[0])} is not finite")
+    bad = np.flatnonzero(~(edges[:-1] < edges[1:]))
+    if bad.size:
+        raise ValueError(f"class_hist: edges must be strictly increasing (edge {int(bad[0]) + 1} <= edge {int(bad[0])})")
+
+
+def class_hist(x: torch.Tensor, target: torch.Tensor, edges, side: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Class-split histogram of x over the sorted edge table `edges` (host, float32, 1 to 2048 strictly
+    increasing finite values): int64 [2, n_edges + 2], row c = target > 0 (0 empty, 1 object), column
+    j = #{k : edges[k] < x} (side 0) or #{k : edges[k] <= x} (side 1) for j <= n_edges; the last
+    column counts the NaN entries of x, which take no slot.  Exact integer counts.
+
+    CUDA tensors run the HIP kernel (tvam_class_hist; `out`, an int64 CUDA tensor of that shape, is
+    overwritten); CPU tensors take a torch path (bucketize + bincount), the one way this module works
+    without a GPU.  target is brought to x's device."""
+    import numpy as np
+    x = torch.as_tensor(x)
+    target = torch.as_tensor(target).to(device=x.device)
+    if x.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError("class_hist: x and target must be float32")
+    if x.numel() != target.numel():
+        raise ValueError("class_hist: x and target must have the same number of elements")
+    x = x.detach().contiguous().reshape(-1)
+    target = target.detach().contiguous().reshape(-1)
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32).reshape(-1))
+    k, n, side = int(e.size), x.numel(), int(side)
+    if x.is_cuda:
+        if out is None:
+            out = torch.empty((2, k + 2), dtype=torch.int64, device=x.device)
+        elif out.dtype != torch.int64 or not out.is_contiguous() or out.device != x.device or out.numel() != 2 * (k + 2):
+            raise ValueError(f"class_hist: out must be a contiguous int64 tensor of shape (2, {k + 2}) on {x.device}")
+        with torch.cuda.device(x.device):
+            _abi.check(_abi.load_library().tvam_class_hist(
+                x.data_ptr() if n else None, target.data_ptr() if n else None, n, e.ctypes.data, k, side,
+                out.data_ptr(), _stream_ptr(x.device)))
+        return out.view(2, k + 2)
+    _check_edges(e, side)
+    nan = torch.isnan(x)
+    slot = torch.bucketize(x, torch.from_numpy(e), right=(side == 1))
+    slot = torch.where(nan, torch.full_like(slot, k + 1), slot)
+    key = slot + (target > 0).to(slot.dtype) * (k + 2)
+    counts = torch.bincount(key, minlength=2 * (k + 2)).to(torch.int64).view(2, k + 2)
+    if out is not None:
+        out.copy_(counts)
+        return out
+    return counts

@@ -41,7 +41,7 @@ from .lbfgs import DirectionPipeline, FusedLinearLBFGS, LinearLBFGS
 from .loss import losses, ThresholdedLoss
 from .optimizers import Adam, SGD
 from .scene import load_dict
-from .utils import discretize, analytic_target, mesh_bbox, target_transform, save_vol, save_img
+from .utils import discretize, analytic_target, mesh_bbox, target_transform, save_vol, save_img, save_histogram
 
 
 def load_scene(config):
@@ -888,11 +888,25 @@ def optimize(config, patterns_fwd=None, device=None):
     pats = prob.gather_patterns(prob.patterns_local().float())
     if prob.rank == 0:
         crop = pats.cpu().numpy().reshape(-1, p.crop[1], p.crop[0])
-        _save_outputs(output, prob, vol_final, full_dmd(p, crop))
-        if prob.surface_aware:  # the binary target on the final sensor's grid (optimize.py:355-360)
-            tb = discretize(prob.scene, sensor=prob.final_sensor).numpy()
+        efficiency, mx = _save_outputs(output, prob, vol_final, full_dmd(p, crop))
+        # the binary target on the final sensor's grid: what the report compares the dose with
+        if prob.surface_aware:  # (optimize.py:355-360)
+            target_for_report = discretize(prob.scene, sensor=prob.final_sensor)
+            tb = target_for_report.numpy()
             np.save(os.path.join(output, "target_binary.npy"), tb)
             save_vol(tb, os.path.join(output, "target_binary.exr"))
+        elif tuple(prob.final_sensor.resolution()) == tuple(prob.sensor.resolution()):
+            target_for_report = prob.target_full
+        elif 'filename' in config['target']:  # a final sensor of another resolution (the reference
+            target_for_report = discretize(prob.scene, sensor=prob.final_sensor)  # fails on the shape mismatch)
+        else:
+            fs = prob.final_sensor
+            target_for_report = analytic_target(fs.resolution(), fs.bbox_min, fs.bbox_max,
+                                                config['target'].get('analytic', 'box_hole'))
+        if mx > 0:  # (optimize.py:362-366)
+            save_histogram(vol_final, target_for_report, os.path.join(output, "histogram.png"), efficiency, mx)
+        else:
+            print("All patterns are zero: no pattern efficiency, no histogram report.")
     return vol_final
 
 
@@ -907,7 +921,8 @@ def full_dmd(p, crop):
 
 def _save_outputs(output, prob, vol_final, full):
     """final.npy / final.exr, loss / timing, patterns/NNNN.exr and patterns(.npz, _normalized_uint8.npz)
-    (optimize.py:330-353)."""
+    (optimize.py:330-353).  Returns the pattern efficiency (0 when every pattern is zero) and the
+    largest pattern value."""
     vf = vol_final.cpu().numpy()
     np.save(os.path.join(output, "final.npy"), vf)
     save_vol(vf, os.path.join(output, "final.exr"))
@@ -919,10 +934,13 @@ def _save_outputs(output, prob, vol_final, full):
         save_img(full[i], os.path.join(output, "patterns", f"{i:04d}.exr"))
     np.savez_compressed(os.path.join(output, "patterns.npz"), patterns=full)
     mx = float(full.max()) if full.size else 0.0
+    efficiency = 0.0
     if mx > 0:
         np.savez_compressed(os.path.join(output, "patterns_normalized_uint8.npz"),
                             patterns=(full / mx * 255).astype(np.uint8))
-        print("Pattern efficiency {:.4f}".format(float(np.sum(full / mx / full.size))))
+        efficiency = float(np.sum(full / mx / full.size))
+        print("Pattern efficiency {:.4f}".format(efficiency))
+    return efficiency, mx
 
 
 def psf_analysis(prob, config, output):

@@ -25,6 +25,107 @@ def iou_loss(pred, target, threshold=0.9):
 
 
 # ---------------------------------------------------------------------------
+# Print report: the IoU sweep and the dose histograms (utils.py:48-81)
+# ---------------------------------------------------------------------------
+def _report_tensors(pred, target):
+    def flat(a):
+        if isinstance(a, np.ndarray):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        return torch.as_tensor(a).detach().to(dtype=torch.float32).reshape(-1)
+    return flat(pred), flat(target)
+
+
+def iou_sweep(pred, target, thresholds=None):
+    """iou_loss(pred, target, t) for every t of `thresholds` (utils.py:59-62; default the
+    reference's np.linspace(0, 1.3, 300) as its fp32 compare sees them) from one pass over the
+    volume: one engine.class_hist(side=0) call, then on the host
+        obj_above[k] = sum_{j > k} counts[1][j], void_above[k] = sum_{j > k} counts[0][j],
+        iou[k] = float32(obj_above[k]) / float32(n_obj + void_above[k])   (0 for an empty union),
+    n_obj counting the object voxels whose dose is NaN too (they are in the union).  Integer counts:
+    the quotients are those of the reference's 300 compare / count passes.  The best threshold is
+    the first maximum (np.argmax).  Returns a dict: thresholds, iou (float32 arrays), best_iou,
+    best_threshold, best_index, n_object, n_empty."""
+    from . import engine
+    th = (np.linspace(0, 1.3, 300) if thresholds is None else np.asarray(thresholds)).astype(np.float32).reshape(-1)
+    x, t = _report_tensors(pred, target)
+    c = engine.class_hist(x, t, th, 0).cpu().numpy()
+    k = th.size
+    # slot j = #{thresholds < x}: x > thresholds[k] <=> j > k (the NaN column stays out)
+    above = np.cumsum(c[:, k:0:-1], axis=1)[:, ::-1]
+    n_obj, n_empty = int(c[1].sum()), int(c[0].sum())
+    union = n_obj + above[0]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        iou = np.where(union > 0, above[1].astype(np.float32) / union.astype(np.float32), np.float32(0.0))
+    iou = iou.astype(np.float32)
+    best = int(np.argmax(iou))
+    return {"thresholds": th, "iou": iou, "best_iou": float(iou[best]), "best_threshold": float(th[best]),
+            "best_index": best, "n_object": n_obj, "n_empty": n_empty}
+
+
+HISTOGRAM_EDGES = 501  # np.linspace(0, 1.3, 501): 500 bins of width 0.0026
+
+
+def save_histogram(vol, target, filename, efficiency, max_pattern_intensity):
+    """The reference's closing report (utils.py:48-81): the IoU of (vol > t) against the target over
+    300 thresholds, its two printed lines, and the dose histograms of object and empty voxels.
+
+    A deliberate departure: the reference bins each class over that class's own min..max
+    (plt.hist(bins=500)), which needs a pass to find the range, makes two runs' histograms
+    incomparable and inherits numpy's uniform-bin arithmetic, which differs between versions.  Here
+    both classes are counted in the fixed half-open bins [e_k, e_k+1) of e = np.linspace(0, 1.3,
+    501).astype(float32), with doses >= e_500 in `above` and NaN doses in `nan`: exact and stable
+    (engine.class_hist, side 1).
+
+    Always written next to `filename`: histogram.npz (edges, object, empty [500], above, nan, below
+    [2] = (empty, object), below: doses under e_0; thresholds, iou) and report.json (best_iou, best_threshold,
+    best_threshold_normalized = best_threshold / max_pattern_intensity, efficiency, n_object,
+    n_empty).  `filename` itself (the PNG: bars from the counts, log y, x in [0, 1.2], the
+    reference's title) only when matplotlib can be imported.  Returns the report dict."""
+    import json
+    from . import engine
+    x, t = _report_tensors(vol, target)
+    print("Finding threshold for best IoU ...")
+    sweep = iou_sweep(x, t)
+    print("Best IoU: {:.4f}".format(sweep["best_iou"]))
+    print("Best threshold: {:4f}".format(sweep["best_threshold"]))
+    edges = np.linspace(0, 1.3, HISTOGRAM_EDGES).astype(np.float32)
+    c = engine.class_hist(x, t, edges, 1).cpu().numpy()
+    k = edges.size
+    # slot j = #{edges <= x}: 0 is below e_0 (negative doses, in neither array), 1..k-1 the bins, k above
+    obj, empty = c[1, 1:k], c[0, 1:k]
+    best_norm = sweep["best_threshold"] / float(max_pattern_intensity)
+    report = {"best_iou": sweep["best_iou"], "best_threshold": sweep["best_threshold"],
+              "best_threshold_normalized": best_norm, "efficiency": float(efficiency),
+              "n_object": sweep["n_object"], "n_empty": sweep["n_empty"]}
+    out_dir = os.path.dirname(os.path.abspath(filename))
+    os.makedirs(out_dir, exist_ok=True)
+    np.savez(os.path.join(out_dir, "histogram.npz"), edges=edges, object=obj, empty=empty, above=c[:, k],
+             nan=c[:, k + 1], below=c[:, 0], thresholds=sweep["thresholds"], iou=sweep["iou"])
+    with open(os.path.join(out_dir, "report.json"), "w") as f:
+        json.dump(report, f, indent=1)
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return report
+    fig = plt.figure(figsize=(10, 5))
+    width = np.diff(edges.astype(np.float64))
+    plt.bar(edges[:-1], obj, width=width, align="edge", label="Object", alpha=0.55)
+    plt.bar(edges[:-1], empty, width=width, align="edge", label="Empty", alpha=0.55)
+    plt.xlim([0, 1.2])
+    plt.title("pattern energy efficiency = {:.4f}, IoU = {:.4f} at threshold = {:.3f}, normalized threshold = {:.3f}"
+              .format(efficiency, sweep["best_iou"], sweep["best_threshold"], best_norm))
+    plt.yscale('log')
+    plt.ylabel("# Voxels")
+    plt.xlabel("Received dose")
+    plt.legend()
+    plt.savefig(filename)
+    plt.close(fig)
+    return report
+
+
+# ---------------------------------------------------------------------------
 # PLY
 # ---------------------------------------------------------------------------
 _PLY_TYPES = {'char': 'b', 'uchar': 'B', 'short': 'h', 'ushort': 'H', 'int': 'i', 'uint': 'I', 'float': 'f',

@@ -627,6 +627,26 @@ int tvam_loss_threshold_probes_mask(const float* dose, const float* ddose,
                                     float w_void, float w_limit, float scale,
                                     double* out, void* hip_stream);
 
+/*
+ * The print report's primitive (drtvam_amd/utils.py: iou_sweep, save_histogram; the reference's
+ * save_histogram, utils.py:8-11, :48-81).  (Added to ABI v13: no struct or existing signature changed.)
+ *
+ * Class-split histogram of x over a sorted edge table.
+ *   class c(i) = target[i] > 0 ? 1 : 0        (object / empty, utils.py:9,50)
+ *   slot  j(i) = side == 0 ? #{k : edges[k] <  x[i]}  (so x > edges[k]  <=>  k < j)
+ *                          : #{k : edges[k] <= x[i]}  (half-open bins [e_k, e_k+1))
+ *   counts[c][j] for j in 0..n_edges; counts[c][n_edges+1] = number of NaN x (NaN takes no slot).
+ *   x, target: device, n floats, any 4-byte alignment.  edges: HOST, n_edges floats.
+ *   counts: device, uint64 [2][n_edges + 2], zeroed by the call.  Synchronises the stream.
+ * The slot comes from fp32 compares alone, so it is exact: -0 equals 0, +-inf land in slot 0 or
+ * n_edges, denormals compare as themselves.  Integer counts: the result does not depend on the order
+ * of the adds.  TVAM_ERR_INVALID (the message names the cause) for a null pointer, n_edges outside
+ * [1, 2048], a non-finite edge, edges that are not strictly increasing, or side not in {0, 1}.
+ * n == 0 (x and target may then be NULL) zeroes counts and launches nothing.
+ */
+int tvam_class_hist(const float* x, const float* target, uint64_t n, const float* edges,
+                    int32_t n_edges, int32_t side, uint64_t* counts, void* hip_stream);
+
 /* Thread-local message describing the last error ("" if none). */
 const char* tvam_last_error(void);
 
