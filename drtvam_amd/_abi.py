@@ -116,7 +116,7 @@ class TvamDesc(ctypes.Structure):
         d = TvamDesc()
         ctypes.pointer(d)[0] = self
         # the triangle arrays and the double vial go with the copy
-        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner", "_double_vial"):
+        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner", "_double_vial", "_traced_vial"):
             if hasattr(self, keep):
                 setattr(d, keep, getattr(self, keep))
         return d
@@ -153,6 +153,17 @@ class TvamDesc(ctypes.Structure):
                                            float(r_int_inner), float(ior_outer), float(ior_inner),
                                            float(ior_inside_inner))
 
+    def set_traced_vial(self, traced: bool = True) -> None:
+        """Mark a 'cylindrical' / 'square' vial descriptor as "trace every ray in 3-D through the glass":
+        engine.Projection then creates its plan through tvam_plan_create_traced (the telecentric and
+        lens projectors need it; a collimated descriptor runs the same per-ray path instead of the
+        planar kernels).  The mark is not part of the C struct."""
+        self._traced_vial = bool(traced)
+
+    @property
+    def traced_vial(self) -> bool:
+        return bool(getattr(self, "_traced_vial", False))
+
     def as_dict(self) -> dict:
         out = {}
         for name, _ in self._fields_:
@@ -171,6 +182,8 @@ EXPORTS = {
     "tvam_mesh_hit": (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, ctypes.c_int64, ctypes.c_int32, _P, _P]),
     "tvam_plan_create_double": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.POINTER(TvamDoubleVial), ctypes.c_int,
                                                ctypes.POINTER(_P)]),
+    "tvam_plan_create_traced": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.c_int, ctypes.POINTER(_P)]),
+    "tvam_traced_segments": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P, _P, ctypes.c_int64, _P]),
     "tvam_plan_segments": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_double_segments": (ctypes.c_int, [ctypes.POINTER(TvamDoubleVial), ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_int32, _P, _P, ctypes.c_int64, _P]),
@@ -328,6 +341,21 @@ def double_segments(vial: TvamDoubleVial, medium_ior, sigma_t, height, max_depth
     segs = np.empty((o.shape[0], 2, 8), np.float32)
     check(load_library().tvam_double_segments(ctypes.byref(vial), float(medium_ior), float(sigma_t), float(height),
                                               int(max_depth), o.ctypes.data, d.ctypes.data, o.shape[0],
+                                              segs.ctypes.data))
+    return segs
+
+
+def traced_segments(desc: TvamDesc, o, d):
+    """Medium segments of world rays (o, d: [n, 3]) behind the 'cylindrical' / 'square' vial of `desc`
+    on the host (tvam_traced_segments, the kernels' own tracer): float32 [n, 8] = o2[0:3], maxt [3],
+    d2[4:7], transmission weight [7]; all zeros where the ray deposits nothing.  No GPU is touched."""
+    import numpy as np
+    o = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("traced_segments: o and d must have the same shape")
+    segs = np.empty((o.shape[0], 8), np.float32)
+    check(load_library().tvam_traced_segments(ctypes.byref(desc), o.ctypes.data, d.ctypes.data, o.shape[0],
                                               segs.ctypes.data))
     return segs
 

@@ -461,9 +461,9 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
     if (!p || (!rays && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     const tvam_desc& d = p->desc;
     if ((d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM &&
-         d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL) ||
+         d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL && !p->traced) ||
         d.albedo != 0.0f || d.n_occluder_tris > 0)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched, 'custom' and 'double_cylindrical' vial plans without scattering or occluders only");
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched, 'custom', 'double_cylindrical' and traced glass vial plans without scattering or occluders only");
     return export_rays(p, active_pixels, n_active, spp, seed, rays, nullptr, stream_);
 }
 
@@ -535,6 +535,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'custom' vial with filter_radon is not implemented on the GPU path");
     if (p->dbl)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_radon is not implemented on the GPU path");
+    if (p->traced)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a traced 'cylindrical' / 'square' vial with filter_radon is not implemented on the GPU path");
     if (p->cone)  // the Radon path is a planar ray (tvam_radon_ray)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "the 'telecentric' / 'lens' projectors with filter_radon are not implemented on the GPU path");
     TvamConsts k;

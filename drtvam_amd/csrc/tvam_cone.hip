@@ -19,7 +19,9 @@
 // instantiated with MESH: the segment comes from cn_segment_mesh (closest hits through the
 // hierarchy, from global memory or from the workgroup's LDS copy), the march takes the refracted
 // direction d2 and the weight em * att.  The index-matched instantiations (MESH = CN_NO_MESH) read
-// d and em as before.
+// d and em as before.  A traced 'cylindrical' / 'square' vial (tvam_plan_create_traced) is one more
+// instantiation, CN_GLASS: the segment comes from tvam_glass.h's analytic tracer, the rest is the
+// mesh instantiations' (d2, em * att); it reads no table.
 #include "tvam_internal.h"
 
 #include <algorithm>
@@ -142,6 +144,9 @@ __global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, Tva
 
 // MESH of a launch and its dynamic LDS.
 static int cn_mesh_mode(const TvamConsts& k) {
+    // (a glass vial reaches these kernels only through a traced plan: tvam_plan_create's plans of
+    // such a vial are planar)
+    if (k.vial_type == TVAM_VIAL_CYLINDRICAL || k.vial_type == TVAM_VIAL_SQUARE) return CN_GLASS;
     return k.vial_type != TVAM_VIAL_CUSTOM ? CN_NO_MESH : (k.mesh.lds_bytes > 0 ? CN_MESH_LDS : CN_MESH_GLOBAL);
 }
 static size_t cn_lds(const TvamConsts& k) { return cn_mesh_mode(k) == CN_MESH_LDS ? cn_mesh_lds_bytes(k.mesh) : 0; }
@@ -174,6 +179,7 @@ hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles&
     switch (cn_mesh_mode(k)) {
         case CN_NO_MESH: cn_launch_rays<CN_NO_MESH>(mode, k, t, pat, idxmap, gin, out, counter, stream); break;
         case CN_MESH_LDS: cn_launch_rays<CN_MESH_LDS>(mode, k, t, pat, idxmap, gin, out, counter, stream); break;
+        case CN_GLASS: cn_launch_rays<CN_GLASS>(mode, k, t, pat, idxmap, gin, out, counter, stream); break;
         default: cn_launch_rays<CN_MESH_GLOBAL>(mode, k, t, pat, idxmap, gin, out, counter, stream);
     }
     return hipGetLastError();
@@ -189,6 +195,9 @@ void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const floa
         case CN_MESH_LDS:
             hipLaunchKernelGGL(tvam_cone_emit_kernel<CN_MESH_LDS>, g, b, cn_lds(k), stream, k, t, pat, idxmap, sb);
             break;
+        case CN_GLASS:
+            hipLaunchKernelGGL(tvam_cone_emit_kernel<CN_GLASS>, g, b, 0, stream, k, t, pat, idxmap, sb);
+            break;
         default:
             hipLaunchKernelGGL(tvam_cone_emit_kernel<CN_MESH_GLOBAL>, g, b, 0, stream, k, t, pat, idxmap, sb);
     }
@@ -202,6 +211,7 @@ hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, cons
         case CN_MESH_LDS:
             hipLaunchKernelGGL(tvam_cone_export_kernel<CN_MESH_LDS>, g, b, cn_lds(k), stream, k, t, idxmap, rays);
             break;
+        case CN_GLASS: hipLaunchKernelGGL(tvam_cone_export_kernel<CN_GLASS>, g, b, 0, stream, k, t, idxmap, rays); break;
         default: hipLaunchKernelGGL(tvam_cone_export_kernel<CN_MESH_GLOBAL>, g, b, 0, stream, k, t, idxmap, rays);
     }
     return hipGetLastError();

@@ -1,9 +1,11 @@
 // tvam_cone_ray.h -- ray generation of the telecentric / lens projectors (projector.py:199-296),
 // shared by tvam_cone.hip (forward, adjoint, export) and tvam_corner.hip (the 'filter_corner'
 // first-hit pass): the sampler draws, get_ray, CircularMotion's to_world and the medium segment
-// behind the index-matched vial, or behind the mesh interfaces of a 'custom' vial, and the per-ray
+// behind the index-matched vial, behind the mesh interfaces of a 'custom' vial or behind the two
+// analytic glass surfaces of a traced 'cylindrical' / 'square' vial (tvam_glass.h), and the per-ray
 // DDA of a 3-D segment (cn_dda), which tvam_cone.hip and tvam_double.hip march (device only).
 #pragma once
+#include "tvam_glass.h"
 #include "tvam_mesh.h"
 #include "tvam_path.h"
 #include "tvam_seg3d.h"
@@ -14,12 +16,14 @@ struct ConeRay {
     float o[3], d[3];  // world-space projector ray
     float o2[3];       // medium segment (o2, d2, [0, maxt])
     float maxt;
-    float d2[3], att;  // 'custom' vial: the refracted direction and the interfaces' transmission weight
+    float d2[3], att;  // 'custom' and traced glass vials: the refracted direction and the interfaces' transmission weight
                        // (index matched: d and 1, and the kernels read d itself)
 };
 
-// How a kernel reads the meshes of a 'custom' vial.
-enum ConeMesh { CN_NO_MESH = 0, CN_MESH_GLOBAL = 1, CN_MESH_LDS = 2 };
+// How a kernel finds the medium segment: behind the index-matched vial, through the meshes of a
+// 'custom' vial (and how it reads them), or through the analytic glass surfaces of a traced
+// 'cylindrical' / 'square' vial (tvam_plan_create_traced).
+enum ConeMesh { CN_NO_MESH = 0, CN_MESH_GLOBAL = 1, CN_MESH_LDS = 2, CN_GLASS = 3 };
 
 // The kernel's view of the meshes: global memory, or the workgroup's LDS copy (the three tables
 // back to back in 16-byte rows; every thread of the workgroup calls this, before its ray loop).
@@ -54,6 +58,11 @@ inline size_t cn_mesh_lds_bytes(const TvamMesh& m) {
 __device__ __forceinline__ bool cn_segment_mesh(const TvamConsts& k, const TvamMeshView& m, ConeRay& r) {
     return tvam_segment_mesh<TVAM_MESH_BRUTE != 0>(m, k.max_depth, k.eta_ext, k.eta_int, r.o, r.d, r.o2, r.d2, r.maxt,
                                                    r.att);
+}
+
+// traced 'cylindrical' / 'square' vial: the medium segment through the two analytic glass surfaces.
+__device__ __forceinline__ bool cn_segment_glass(const TvamConsts& k, ConeRay& r) {
+    return tvam_segment_traced(k, r.o, r.d, r.o2, r.d2, r.maxt, r.att);
 }
 
 // Mitsuba warp::square_to_uniform_disk_concentric (Shirley & Chiu), restated
@@ -110,6 +119,7 @@ __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& 
         tvam_ray_world(k, c, sn, xc, yc, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1]);
         r.d[2] = 0.0f;
         if (RAY_ONLY) return true;
+        if (MESH == CN_GLASS) return cn_segment_glass(k, r);
         if (MESH != CN_NO_MESH) return cn_segment_mesh(k, *mesh, r);
         r.o2[2] = r.o[2];
         return tvam_segment_im(k, r.o[0], r.o[1], r.o[2], r.d[0], r.d[1], r.o2[0], r.o2[1], r.maxt);
@@ -148,6 +158,7 @@ __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& 
     r.d[1] = -sn * vz - c * vx;
     r.d[2] = vy;
     if (RAY_ONLY) return true;
+    if (MESH == CN_GLASS) return cn_segment_glass(k, r);
     if (MESH != CN_NO_MESH) return cn_segment_mesh(k, *mesh, r);
     return cn_segment(k, r);
 }

@@ -44,6 +44,7 @@ struct tvam_plan {
     const float* vols = nullptr;  // caller's compute_volume() output (tvam_plan_set_volumes)
     TvamDevBuf<float> tgt, occ;   // target mesh (surface-aware films) and occluder triangles
     bool dbl = false;        // 'double_cylindrical' vial: four tubes traced per ray, two segments (tvam_double.h); implies cone
+    bool traced = false;     // 'cylindrical' / 'square' vial traced per ray in 3-D (tvam_plan_create_traced, tvam_glass.h); implies cone
     TvamDevBuf<float4> mesh_nodes;  // 'custom' vial: the hierarchy over both meshes (TvamMesh)
     TvamDevBuf<float> mesh_tris;
     TvamDevBuf<int32_t> mesh_ids;

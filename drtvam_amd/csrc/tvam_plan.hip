@@ -8,6 +8,7 @@
 //   * per-z-slice list of DMD rows whose (planar) rays lie in that slice;
 //   * per-(xy-tile, angle) range of DMD columns whose rays can cross the tile.
 #include "tvam_plan.h"
+#include "tvam_glass.h"
 #include "tvam_mesh.h"
 
 #include <algorithm>
@@ -80,11 +81,15 @@ extern "C" void tvam_plan_destroy(tvam_plan* p) {
     (void)hipSetDevice(cur);
 }
 
-static int validate(const tvam_desc& d) {
+// traced: the descriptor of tvam_plan_create_traced (a 'cylindrical' / 'square' vial on the 3-D
+// per-ray path, any projector kind)
+static int validate(const tvam_desc& d, bool traced = false) {
     if (d.abi_version != TVAM_ABI_VERSION) return tvam_fail(TVAM_ERR_INVALID, "tvam_desc.abi_version mismatch");
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED && d.projector_type != TVAM_PROJECTOR_TELECENTRIC &&
         d.projector_type != TVAM_PROJECTOR_LENS)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'collimated', 'telecentric' and 'lens' projectors are implemented on the GPU path");
+    if (traced && d.vial_type != TVAM_VIAL_CYLINDRICAL && d.vial_type != TVAM_VIAL_SQUARE)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_traced: vial_type must be TVAM_VIAL_CYLINDRICAL or TVAM_VIAL_SQUARE (other vials: tvam_plan_create and its siblings)");
     if (d.vial_type == TVAM_VIAL_CUSTOM) {
         // mesh vial (tvam_plan_create_mesh): every ray is traced in 3-D through the interfaces and
         // runs the per-ray kernels of tvam_cone.hip, whose limits these are
@@ -130,6 +135,32 @@ static int validate(const tvam_desc& d) {
             return no("rr_depth < min(max_depth, 7) - 1 (Russian roulette on or before a deposit)");
         if (!(d.vial_height > 0.0f))
             return tvam_fail(TVAM_ERR_INVALID, "a 'double_cylindrical' vial needs a positive height");
+    } else if (traced) {
+        // glass tube or cuvette traced per ray (tvam_plan_create_traced): every ray is traced in 3-D
+        // through the two analytic surfaces (tvam_glass.h) and runs the per-ray kernels of
+        // tvam_cone.hip, whose limits these are
+        const char* pn = d.projector_type == TVAM_PROJECTOR_LENS          ? "'lens'"
+                         : d.projector_type == TVAM_PROJECTOR_TELECENTRIC ? "'telecentric'"
+                                                                          : "'collimated'";
+        auto no = [&](const char* what) {
+            return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string("the ") + pn + " projector with " + what +
+                                                  " behind a traced glass vial is not implemented on the GPU path");
+        };
+        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
+            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
+            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
+        }
+        if (!(d.vial_r > 0.0f && d.vial_r_ext > d.vial_r && d.vial_ior > 0.0f && d.medium_ior > 0.0f &&
+              d.vial_height > 0.0f))
+            return tvam_fail(TVAM_ERR_INVALID, "glass vial: need r_ext > r_int > 0 (w_ext > w_int), a positive height and positive IORs");
+        if (d.n_occluder_tris > 0) return no("occluders");
+        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
+        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
+        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
+        if (d.film_channels == 2) return no("a surface-aware film");
+        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
+        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
+        if (d.rr_depth < 2) return no("rr_depth < 2 (Russian roulette before the medium segment)");
     } else if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
         // 3-D projector rays (tvam_cone.hip): index-matched vial, absorbing medium, 'dda' sensor,
         // one-channel film, the whole film
@@ -140,8 +171,12 @@ static int validate(const tvam_desc& d) {
         };
         if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
         if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
-        if (d.vial_type == TVAM_VIAL_CYLINDRICAL) return no("a 'cylindrical' vial (3-D refraction)");
-        if (d.vial_type == TVAM_VIAL_SQUARE) return no("a 'square' vial (3-D refraction)");
+        // (3-D refraction at the glass: the traced entry's, with its own limits)
+        if (d.vial_type == TVAM_VIAL_CYLINDRICAL || d.vial_type == TVAM_VIAL_SQUARE)
+            return tvam_fail(TVAM_ERR_UNSUPPORTED,
+                             std::string("the ") + pn + " projector with a " +
+                                 (d.vial_type == TVAM_VIAL_SQUARE ? "'square'" : "'cylindrical'") +
+                                 " vial (3-D refraction) needs the traced path: create the plan with tvam_plan_create_traced");
         if (d.n_occluder_tris > 0) return no("occluders");
         if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
         if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
@@ -394,10 +429,14 @@ static int planar_tables(tvam_plan* p, const std::vector<float2>& cs, TvamDevBuf
     // occluders end segments at z-dependent points: rows no longer share a path
     if (!d.regular_sampling || (d.flags & TVAM_FLAG_NO_PLANAR) || p->empty || d.n_occluder_tris > 0) return 0;
     std::vector<std::vector<int32_t>> rows_of(k.nz);
+    // a square vial's inner cuboid is lower than its outer one (vial_hz_int): a planar ray between
+    // the two heights crosses glass alone and deposits nothing (tvam_segment_square's inner hit
+    // fails its z test), so such a row shares no column chord
+    const float row_half = d.vial_type == TVAM_VIAL_SQUARE ? std::min(k.vial_half_h, k.vial_hz_int) : k.vial_half_h;
     for (int rc = 0; rc < d.crop_y; ++rc) {
         float yc;
         const int s = regular_row_slice(d, k, rc, yc);
-        if (s < 0 || s >= k.nz || !(yc >= -k.vial_half_h && yc <= k.vial_half_h)) continue;  // misses grid / vial / slab
+        if (s < 0 || s >= k.nz || !(yc >= -row_half && yc <= row_half)) continue;  // misses grid / vial / slab
         if (!(std::fabs(yc) <= 0.7f * d.vial_r)) return 0;  // spawn offset would depend on z
         rows_of[s].push_back(rc);
     }
@@ -1252,7 +1291,7 @@ static int upload_vial_meshes(tvam_plan* p, const float* outer, int32_t n_outer,
 }
 
 static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
-                       const tvam_double_vial* dbl, int device, tvam_plan** out);
+                       const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced = false);
 // tvam_double.hip
 int tvam_double_validate(const tvam_double_vial* v, float medium_ior);
 TvamDouble tvam_double_consts(const tvam_double_vial& v, float medium_ior);
@@ -1279,6 +1318,31 @@ extern "C" int tvam_plan_create_double(const tvam_desc* desc, const tvam_double_
     return plan_create(*desc, nullptr, 0, nullptr, 0, vial, device, out);
 }
 
+extern "C" int tvam_plan_create_traced(const tvam_desc* desc, int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out, true);
+}
+
+// The host tracer of such a plan (tvam_glass.h), ray by ray: no device call.
+extern "C" int tvam_traced_segments(const tvam_desc* desc, const float* o, const float* d, int64_t n_rays,
+                                    float* segs) {
+    if (!desc || n_rays < 0 || (n_rays > 0 && (!o || !d || !segs))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (validate(*desc, true)) return TVAM_ERR_INVALID;  // (the message is the plan entry's)
+    const TvamConsts k = make_consts(*desc, 0, 0);
+    for (int64_t i = 0; i < n_rays; ++i) {
+        float o2[3], d2[3], maxt, att;
+        float* s = segs + 8 * i;
+        if (tvam_segment_traced(k, o + 3 * i, d + 3 * i, o2, d2, maxt, att)) {
+            s[0] = o2[0], s[1] = o2[1], s[2] = o2[2], s[3] = maxt;
+            s[4] = d2[0], s[5] = d2[1], s[6] = d2[2], s[7] = att;
+        } else {
+            for (int j = 0; j < 8; ++j) s[j] = 0.0f;
+        }
+    }
+    return 0;
+}
+
 extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_t n_outer,
                                      const float* inner_tris, int32_t n_inner, int device, tvam_plan** out) {
     if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
@@ -1295,13 +1359,13 @@ extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_t
 }
 
 static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_outer, const float* inner,
-                       int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out) {
+                       int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced) {
     tvam_desc d = d_in;
     if (dbl) {  // the host tables (tiles, slots) are sized by the medium's tube and the outermost one
         d.vial_r = dbl->r_int_outer;
         d.vial_r_ext = dbl->r_ext_outer;
     }
-    int rc = validate(d);
+    int rc = validate(d, traced);
     if (rc) return rc;
     int a0 = d.angle_begin, a1 = d.angle_end < 0 ? d.n_patterns : d.angle_end;
     if (a0 < 0 || a1 > d.n_patterns || a0 > a1) return tvam_fail(TVAM_ERR_INVALID, "invalid angle shard");
@@ -1328,7 +1392,9 @@ static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_oute
         p->empty = d.max_depth < 3;  // the first deposit is at loop iteration 2
         p->k.dbl = tvam_double_consts(*dbl, d.medium_ior);
     }
-    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh || p->dbl;
+    p->traced = traced;
+    if (traced) p->cyl = false;  // (the planar tables and ray records of a refracting vial are not this path's)
+    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh || p->dbl || traced;
     p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
     if ((rc = upload_meshes(p.get())) || (rc = tile_geometry(p.get()))) return rc;
     if (p->mesh && (rc = upload_vial_meshes(p.get(), outer, n_outer, inner, n_inner))) return rc;
@@ -1417,6 +1483,8 @@ extern "C" int tvam_row_slices(const tvam_desc* desc, int32_t* slice_of_row) {
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: a 'custom' vial's rays leave their slice (no film slabs)");
     if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL)  // per-ray 3-D kernels: no film slabs
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_row_slices: a 'double_cylindrical' vial runs the 3-D per-ray path (no film slabs)");
+    // (a descriptor meant for tvam_plan_create_traced is a planar one here when collimated, and is
+    // refused above with the projector's message otherwise: that path has no film slabs either)
     const TvamConsts k = make_consts(d, 0, d.n_patterns);
     for (int r = 0; r < d.crop_y; ++r) {
         float xc, yc;

@@ -63,6 +63,9 @@ class Projection:
                 _abi.check(self.lib.tvam_plan_create_double(
                     ctypes.byref(self.desc), None if vial is None else ctypes.byref(vial), self.device.index,
                     ctypes.byref(plan)))
+            elif self.desc.traced_vial:  # glass tube / cuvette traced per ray in 3-D (set_traced_vial)
+                _abi.check(self.lib.tvam_plan_create_traced(ctypes.byref(self.desc), self.device.index,
+                                                            ctypes.byref(plan)))
             else:
                 _abi.check(self.lib.tvam_plan_create(ctypes.byref(self.desc), self.device.index, ctypes.byref(plan)))
         self._plan = plan
@@ -235,8 +238,8 @@ class Projection:
         """The projector rays of a call (tvam_plan_rays), [n_active * spp, 16] float32 in sampler-stream
         order (row = active entry * spp + sample): o[0:3], d[3:6], hit [6], o2[7:10], maxt [10],
         d2[11:14], weight [14] (the whole per-ray weight), 0.  The diagnostic counterpart of the
-        oracle's ray(); index-matched plans with a non-scattering medium, and 'custom' and
-        'double_cylindrical' vial plans (d2: the refracted direction; the weight carries the
+        oracle's ray(); index-matched plans with a non-scattering medium, and 'custom',
+        'double_cylindrical' and traced glass vial plans (d2: the refracted direction; the weight carries the
         interfaces' transmission; double_cylindrical: the first of the two segments, see segments())."""
         if active_pixels is not None:
             self._check_pixels(active_pixels)
@@ -276,8 +279,8 @@ class Projection:
 
     @property
     def cone(self) -> bool:
-        """True for the 3-D per-ray path: a telecentric / lens projector, or a 'custom' or
-        'double_cylindrical' vial."""
+        """True for the 3-D per-ray path: a telecentric / lens projector, a 'custom' or
+        'double_cylindrical' vial, or a traced 'cylindrical' / 'square' vial (set_traced_vial)."""
         return bool(self.lib.tvam_plan_path(self._plan) & 4)
 
     @property

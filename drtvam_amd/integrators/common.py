@@ -42,6 +42,10 @@ class TVAMIntegrator:
         projector.fill_desc(d)
         sensor.fill_desc(d)
         scene.container.fill_desc(d)
+        # a telecentric / lens projector behind a glass tube or cuvette: 3-D refraction, the traced
+        # plan entry (tvam_plan_create_traced); collimated configs keep their planar kernels
+        if d.vial_type in (_abi.VIAL_CYLINDRICAL, _abi.VIAL_SQUARE) and d.projector_type != _abi.PROJECTOR_COLLIMATED:
+            d.set_traced_vial()
         d.print_time = float(self.print_time)
         d.regular_sampling = int(bool(self.regular_sampling))
         d.sample_time = int(bool(self.sample_time))
@@ -67,7 +71,7 @@ class TVAMIntegrator:
         from ..engine import Projection
         d = self.desc(scene, sensor)
         dev = torch.device(device) if device is not None else scene.projector.device
-        key = (bytes(memoryview(ctypes.string_at(ctypes.addressof(d), ctypes.sizeof(d)))), str(dev))
+        key = (bytes(memoryview(ctypes.string_at(ctypes.addressof(d), ctypes.sizeof(d)))), d.traced_vial, str(dev))
         proj = self._plans.get(key)
         if proj is None:
             proj = Projection(d, dev)

@@ -268,6 +268,35 @@ int tvam_double_segments(const tvam_double_vial* vial, float medium_ior, float s
                          int32_t max_depth, const float* o, const float* d, int64_t n_rays, float* segs);
 
 /*
+ * A plan behind a 'cylindrical' or 'square' glass vial whose rays are traced in 3-D (vial_type =
+ * TVAM_VIAL_CYLINDRICAL or TVAM_VIAL_SQUARE, any projector kind): the entry for the telecentric and
+ * lens projectors behind a glass tube or cuvette, which tvam_plan_create refuses, naming this one.
+ * Every ray is traced through the two analytic dielectric surfaces (volume.py:179-272 in
+ * transmission-only mode: nearest hit of the outer and the inner surface, a tie to the inner one,
+ * Fresnel transmission, spawn offset, medium flag, at most max_depth surfaces) to its one medium
+ * segment, and the plan runs the per-ray 3-D kernels.  cylindrical: open tubes of radius vial_r_ext
+ * and vial_r with |z| <= vial_height / 2 and no end caps, so a ray may enter or leave through an open
+ * end (one that leaves the medium that way deposits nothing); square: closed cuboids of half width
+ * vial_r_ext and vial_r, the inner one 0.9 of the height, all six faces.  A collimated descriptor
+ * through this entry runs the same 3-D path (tvam_plan_create gives it the planar kernels).
+ * TVAM_ERR_UNSUPPORTED, as "the '<kind>' projector with <what>": occluders, albedo > 0, the ratio /
+ * delta sensors, a surface-aware film, film slabs, transmission_only = 0, rr_depth < 2.
+ * TVAM_ERR_INVALID: any other vial type, r_ext <= r_int, non-positive radii / height / IORs, a bad
+ * focus_distance / aperture_radius.  All of it is checked before any device call.  On such a plan
+ * tvam_plan_rays gives d2 in [11:14] and weight x the interfaces' transmission in [14]; tvam_radon
+ * refuses it; tvam_corner serves it.
+ */
+int tvam_plan_create_traced(const tvam_desc* desc, int device, tvam_plan** plan);
+
+/*
+ * The medium segments of such a plan's tracer on the host, with the code the kernels run and no GPU
+ * touched: n_rays world rays (o, d: [n_rays][3], host), segs: host [n_rays][8] = o2[3], maxt, d2[3],
+ * att (the interfaces' transmission weight); a row is all zeros when the ray deposits nothing.
+ * TVAM_ERR_INVALID for a descriptor tvam_plan_create_traced would refuse.
+ */
+int tvam_traced_segments(const tvam_desc* desc, const float* o, const float* d, int64_t n_rays, float* segs);
+
+/*
  * Forward projection (primal render).  Writes the whole film
  * dose[z][y][x][C] (film order) = inv_vol * sum over rays of this plan's
  * angle shard; every voxel is overwritten (no pre-zeroing needed).
