@@ -42,6 +42,8 @@ FLAG_RAY_FWD = 8
 FLAG_SCATTER_ATOMIC = 16
 FLAG_BIN_FIRST = 32
 LBFGS_WORK_DOUBLES = 2048 * 64
+LOSS_KIND_THRESHOLD = 0
+LOSS_KIND_L2 = 1
 
 
 class TvamDoubleVial(ctypes.Structure):
@@ -254,6 +256,19 @@ EXPORTS = {
     "tvam_loss_threshold_probes_mask": (
         ctypes.c_int,
         [_P, _P, _P, ctypes.c_int32, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_float,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P],
+    ),
+    "tvam_loss_square": (ctypes.c_int, [_P, _P, ctypes.c_float, _P, ctypes.c_uint64, ctypes.c_float, _P, _P, _P]),
+    "tvam_loss_square_probes": (
+        ctypes.c_int, [_P, _P, _P, ctypes.c_int32, _P, ctypes.c_uint64, ctypes.c_float, _P, _P]),
+    "tvam_loss_surface": (
+        ctypes.c_int,
+        [ctypes.c_int32, _P, _P, ctypes.c_float, _P, ctypes.c_uint64, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P],
+    ),
+    "tvam_loss_surface_probes": (
+        ctypes.c_int,
+        [ctypes.c_int32, _P, _P, _P, ctypes.c_int32, _P, ctypes.c_uint64, ctypes.c_int32, ctypes.c_float,
          ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P],
     ),
     "tvam_class_hist": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _P, ctypes.c_int32, ctypes.c_int32, _P, _P]),

@@ -350,3 +350,15 @@ hipError_t tvam_launch_gather(const TvamConsts& k, const float* dense, const uin
                               uint64_t n, float* out, hipStream_t stream);
 
 #define TVAM_MAX_PROBES 8
+
+// step sizes of a probe kernel (tvam_loss_*_probes), passed by value
+struct TvamProbeAlphas {
+    float a[TVAM_MAX_PROBES];
+};
+
+// x^K as K fp32 products in order (r = 1; r *= x): the loss kernels' integer power
+__device__ __forceinline__ float tvam_powi(float x, int K) {
+    float r = 1.0f;
+    for (int i = 0; i < K; ++i) r *= x;
+    return r;
+}

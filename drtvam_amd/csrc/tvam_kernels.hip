@@ -704,12 +704,6 @@ hipError_t tvam_launch_gather(const TvamConsts& k, const float* dense, const uin
 // ---------------------------------------------------------------------------
 // ThresholdedLoss (loss.py:82-132), binary target: fused value + gradient.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float tvam_powi(float x, int K) {
-    float r = 1.0f;
-    for (int i = 0; i < K; ++i) r *= x;
-    return r;
-}
-
 // The object test of a voxel: target > 0 (loss.py:119), from the f32 target or from its bit mask
 // (tvam_target_mask: bit i of word i / 32 = target[i] > 0, read at bit offset mbit0 + i): the same
 // predicate from 1/32 of the bytes.
@@ -823,10 +817,6 @@ __global__ __launch_bounds__(256) void tvam_loss_threshold_kernel(
 // Armijo probes of the linear line search (lbfgs.py:255-268): the loss of dose + alpha_j * ddose for
 // up to TVAM_MAX_PROBES step sizes in one pass over dose / ddose / target (per element the same
 // arithmetic as tvam_loss_threshold_kernel), out[j] += sum_j * scale.
-struct TvamProbeAlphas {
-    float a[TVAM_MAX_PROBES];
-};
-
 template <int KC>
 __device__ __forceinline__ float tvam_loss_elem(float x, bool obj, int Kr, float tl, float tu, float w_object,
                                                 float w_void, float w_limit) {

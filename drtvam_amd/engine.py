@@ -476,6 +476,95 @@ def loss_threshold(dose: torch.Tensor, target: torch.Tensor, K: int, tl: float, 
     return out[0]
 
 
+def _check_loss_tensors(what, dose, n_floats, **tensors):
+    """The loss wrappers' checks: contiguous float32 tensors on dose's device, n_floats each."""
+    for name, t in (("dose", dose),) + tuple(tensors.items()):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dose.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor on {dose.device}")
+        if t is not None and t.numel() != n_floats:
+            raise ValueError(f"{what}: size mismatch")
+
+
+def _probe_alphas(what, alphas):
+    na = len(alphas)
+    if not 1 <= na <= 8:
+        raise ValueError(f"{what}: 1 to 8 step sizes")
+    return na, (ctypes.c_float * na)(*[float(v) for v in alphas])
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def loss_square(dose: torch.Tensor, target: torch.Tensor, scale: float, ddose: Optional[torch.Tensor] = None,
+                alpha: float = 0.0, grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fused L2Loss over a one-channel target (tvam_loss_square): scale * sum (x - target)^2 with x = dose +
+    alpha * ddose as an f64 device scalar, and optionally dL/dx = 2 (x - target) scale into grad."""
+    lib = _abi.load_library()
+    n = dose.numel()
+    _check_loss_tensors("loss_square", dose, n, target=target, ddose=ddose, grad=grad)
+    out = torch.zeros(1, dtype=torch.float64, device=dose.device)
+    with torch.cuda.device(dose.device):
+        _abi.check(lib.tvam_loss_square(dose.data_ptr(), _ptr(ddose), float(alpha), target.data_ptr(), n, float(scale),
+                                        out.data_ptr(), _ptr(grad), _stream_ptr(dose.device)))
+    return out[0]
+
+
+def loss_square_probes(dose: torch.Tensor, ddose: torch.Tensor, alphas, target: torch.Tensor,
+                       scale: float) -> torch.Tensor:
+    """loss_square of dose + a * ddose for each a in alphas (<= 8): f64 device vector, one pass."""
+    lib = _abi.load_library()
+    na, a = _probe_alphas("loss_square_probes", alphas)
+    n = dose.numel()
+    _check_loss_tensors("loss_square_probes", dose, n, ddose=ddose, target=target)
+    out = torch.zeros(na, dtype=torch.float64, device=dose.device)
+    with torch.cuda.device(dose.device):
+        _abi.check(lib.tvam_loss_square_probes(dose.data_ptr(), ddose.data_ptr(), a, na, target.data_ptr(), n,
+                                               float(scale), out.data_ptr(), _stream_ptr(dose.device)))
+    return out
+
+
+def _surface_voxels(what, dose):
+    if dose.numel() % 2:
+        raise ValueError(f"{what}: a two-channel dose has an even number of floats")
+    return dose.numel() // 2
+
+
+def loss_surface(kind: int, dose: torch.Tensor, target: torch.Tensor, scale: float, K: int = 2, tl: float = 0.0,
+                 tu: float = 0.0, w_object: float = 1.0, w_void: float = 1.0, w_limit: float = 1.0,
+                 ddose: Optional[torch.Tensor] = None, alpha: float = 0.0,
+                 grad: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Fused loss over a surface-aware film (tvam_loss_surface): dose, target, ddose, grad hold the two
+    channels interleaved per voxel ([..., 2]); kind _abi.LOSS_KIND_THRESHOLD (K, tl, tu and the weights
+    of ThresholdedLoss) or _abi.LOSS_KIND_L2.  f64 device scalar; dL/dx per channel into grad."""
+    lib = _abi.load_library()
+    nv = _surface_voxels("loss_surface", dose)
+    _check_loss_tensors("loss_surface", dose, 2 * nv, target=target, ddose=ddose, grad=grad)
+    out = torch.zeros(1, dtype=torch.float64, device=dose.device)
+    with torch.cuda.device(dose.device):
+        _abi.check(lib.tvam_loss_surface(
+            int(kind), dose.data_ptr(), _ptr(ddose), float(alpha), target.data_ptr(), nv, int(K), float(tl), float(tu),
+            float(w_object), float(w_void), float(w_limit), float(scale), out.data_ptr(), _ptr(grad),
+            _stream_ptr(dose.device)))
+    return out[0]
+
+
+def loss_surface_probes(kind: int, dose: torch.Tensor, ddose: torch.Tensor, alphas, target: torch.Tensor,
+                        scale: float, K: int = 2, tl: float = 0.0, tu: float = 0.0, w_object: float = 1.0,
+                        w_void: float = 1.0, w_limit: float = 1.0) -> torch.Tensor:
+    """loss_surface of dose + a * ddose for each a in alphas (<= 8): f64 device vector, one pass."""
+    lib = _abi.load_library()
+    na, a = _probe_alphas("loss_surface_probes", alphas)
+    nv = _surface_voxels("loss_surface_probes", dose)
+    _check_loss_tensors("loss_surface_probes", dose, 2 * nv, ddose=ddose, target=target)
+    out = torch.zeros(na, dtype=torch.float64, device=dose.device)
+    with torch.cuda.device(dose.device):
+        _abi.check(lib.tvam_loss_surface_probes(
+            int(kind), dose.data_ptr(), ddose.data_ptr(), a, na, target.data_ptr(), nv, int(K), float(tl), float(tu),
+            float(w_object), float(w_void), float(w_limit), float(scale), out.data_ptr(), _stream_ptr(dose.device)))
+    return out
+
+
 def _check_edges(edges, side: int) -> None:
     """tvam_class_hist's argument checks, for the torch path (the CUDA path leaves them to the library)."""
     import numpy as np

@@ -9,7 +9,10 @@ separately.  Gradients come from torch autograd.
 ``ThresholdedLoss.fused_value`` / ``fused_value_grad`` evaluate the binary-
 target case with one HIP kernel pass (value + dL/dx), which is what the
 optimizer uses on the GPU for the main evaluation and the Armijo probes of
-lbfgs.py:256-266 (x = vol + alpha * dvol, never materialised).
+lbfgs.py:256-266 (x = vol + alpha * dvol, never materialised).  ``L2Loss`` has
+the same three methods (tvam_loss_square), and both classes serve a two-channel
+surface-aware target through tvam_loss_surface; ``__call__`` stays the torch
+definition of every one of them.
 """
 from __future__ import annotations
 
@@ -26,6 +29,11 @@ def _sum(x):
 
 def _mean(x):
     return torch.mean(x)
+
+
+def _channels(x, target) -> int:
+    """2 for a surface-aware pair (x and target both [..., 2]), else 1 (Loss.__call__'s cases)."""
+    return 2 if x.dim() > 1 and tuple(x.shape) == tuple(target.shape) and x.shape[-1] == 2 else 1
 
 
 class Loss:
@@ -70,6 +78,11 @@ class Loss:
                              "The last dimension should be either 1 or 2.")
         return self.reduction(loss) + self.reduction(loss_patterns)
 
+    def _fused_scale(self, x, target, count):
+        """The kernels' scale: 1, or for 'mean' 1 / voxels (``count``: of the whole film when x is
+        one slab of it; a two-channel voxel counts once, as the mean over w_in * .. + w_out * ..)."""
+        return 1.0 / (count or x.numel() // _channels(x, target)) if self.reduction_name == 'mean' else 1.0
+
 
 class L2Loss(Loss):
     def __init__(self, props):
@@ -88,6 +101,49 @@ class L2Loss(Loss):
 
     def eval_sparsity(self, patterns):
         return patterns ** self.M * self.weight_sparsity
+
+    # ---- fused HIP path (greyscale target, or a two-channel surface-aware one) -------------
+    def fusable(self, x, target) -> bool:
+        return (x.is_cuda and x.dtype == torch.float32 and target.dtype == torch.float32
+                and target.numel() == x.numel())
+
+    def _sparsity_value(self, x, target, patterns):
+        # eval() has no sparsity term (0 * patterns); the two-channel form has eval_sparsity's
+        if not self.weight_sparsity or patterns is None or _channels(x, target) == 1:
+            return None
+        return self.reduction(self.eval_sparsity(patterns.detach())).to(torch.float64)
+
+    def _fused(self, x, target, patterns, count, dx=None, alpha=0.0, alphas=None, grad=None):
+        from . import engine
+        from ._abi import LOSS_KIND_L2
+        scale = self._fused_scale(x, target, count)
+        xf, tf = x.reshape(-1), target.reshape(-1)
+        dxf = None if dx is None else dx.reshape(-1)
+        if _channels(x, target) == 2:
+            v = (engine.loss_surface_probes(LOSS_KIND_L2, xf, dxf, alphas, tf, scale) if alphas is not None else
+                 engine.loss_surface(LOSS_KIND_L2, xf, tf, scale, ddose=dxf, alpha=alpha,
+                                     grad=None if grad is None else grad.reshape(-1)))
+        else:
+            v = (engine.loss_square_probes(xf, dxf, alphas, tf, scale) if alphas is not None else
+                 engine.loss_square(xf, tf, scale, ddose=dxf, alpha=alpha, grad=None if grad is None else grad.reshape(-1)))
+        s = self._sparsity_value(x, target, patterns)
+        return v if s is None else v + s
+
+    def fused_value(self, x, target, patterns, dx=None, alpha=0.0, count=None):
+        """Loss of x (+ alpha*dx) as an f64 device scalar, one kernel pass.  ``patterns=None``
+        leaves out the sparsity term; ``count`` is the voxel count of a 'mean' reduction
+        when x is one slab of the film."""
+        return self._fused(x, target, patterns, count, dx=dx, alpha=alpha)
+
+    def fused_values(self, x, target, patterns, dx, alphas, count=None):
+        """Losses of x + a*dx for every a in alphas (<= 8) as an f64 device vector, one kernel
+        pass (the Armijo probes of the line search; ``patterns`` / ``count`` as in fused_value)."""
+        return self._fused(x, target, patterns, count, dx=dx, alphas=alphas)
+
+    def fused_value_grad(self, x, target, patterns, grad_out, count=None):
+        """Loss value (f64 device scalar) and dL/dx written into grad_out, one kernel pass
+        (``patterns`` / ``count`` as in fused_value)."""
+        return self._fused(x, target, patterns, count, grad=grad_out)
 
 
 class ThresholdedLoss(Loss):
@@ -145,10 +201,29 @@ class ThresholdedLoss(Loss):
             self._mask_cache = c
         return c[2], (target.data_ptr() - base.data_ptr()) // 4
 
+    def _fused_surface(self, x, target, patterns, count, dx=None, alpha=0.0, alphas=None, grad=None):
+        """The three fused methods over a two-channel surface-aware target (tvam_loss_surface)."""
+        from . import engine
+        from ._abi import LOSS_KIND_THRESHOLD
+        scale = self._fused_scale(x, target, count)
+        par = dict(K=int(self.K), tl=self.tl, tu=self.tu, w_object=self.weight_object, w_void=self.weight_void,
+                   w_limit=self.weight_limit)
+        xf, tf = x.reshape(-1), target.reshape(-1)
+        dxf = None if dx is None else dx.reshape(-1)
+        if alphas is not None:
+            v = engine.loss_surface_probes(LOSS_KIND_THRESHOLD, xf, dxf, alphas, tf, scale, **par)
+        else:
+            v = engine.loss_surface(LOSS_KIND_THRESHOLD, xf, tf, scale, ddose=dxf, alpha=alpha,
+                                    grad=None if grad is None else grad.reshape(-1), **par)
+        s = self._sparsity_value(patterns)
+        return v if s is None else v + s
+
     def fused_value(self, x, target, patterns, dx=None, alpha=0.0, count=None):
         """Loss of x (+ alpha*dx) as an f64 device scalar, one kernel pass.  ``patterns=None``
         leaves out the sparsity term; ``count`` is the element count of a 'mean' reduction
         when x is one slab of the film."""
+        if _channels(x, target) == 2:
+            return self._fused_surface(x, target, patterns, count, dx=dx, alpha=alpha)
         from .engine import loss_threshold
         scale = 1.0 / (count or x.numel()) if self.reduction_name == 'mean' else 1.0
         m = self._target_mask(target)
@@ -162,6 +237,8 @@ class ThresholdedLoss(Loss):
     def fused_values(self, x, target, patterns, dx, alphas, count=None):
         """Losses of x + a*dx for every a in alphas (<= 8) as an f64 device vector, one kernel
         pass (the Armijo probes of the line search; ``patterns`` / ``count`` as in fused_value)."""
+        if _channels(x, target) == 2:
+            return self._fused_surface(x, target, patterns, count, dx=dx, alphas=alphas)
         from .engine import loss_threshold_probes
         scale = 1.0 / (count or x.numel()) if self.reduction_name == 'mean' else 1.0
         m = self._target_mask(target)
@@ -174,6 +251,8 @@ class ThresholdedLoss(Loss):
     def fused_value_grad(self, x, target, patterns, grad_out, count=None):
         """Loss value (f64 device scalar) and dL/dx written into grad_out, one kernel pass
         (``patterns`` / ``count`` as in fused_value)."""
+        if _channels(x, target) == 2:
+            return self._fused_surface(x, target, patterns, count, grad=grad_out)
         from .engine import loss_threshold
         scale = 1.0 / (count or x.numel()) if self.reduction_name == 'mean' else 1.0
         m = self._target_mask(target)

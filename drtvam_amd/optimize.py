@@ -9,9 +9,10 @@ optimize.py:15-79 (vial, projector, sensor with scalex/y/z, target transform).
     -> adjoint render -> LinearLBFGS.step (1 more forward render + Armijo)
     -> clamp patterns at 0
 
-With ThresholdedLoss on a binary target the loss, its gradient and every
-Armijo probe run in the fused HIP loss kernel; other losses go through torch
-autograd with the same render op.  Under torch.distributed the projector
+With ThresholdedLoss (integer K) or L2Loss, over a one-channel or a surface-
+aware target, the loss, its gradient and every Armijo probe run in the fused
+HIP loss kernels; a non-integer K, or the config's 'fused_loss': false, goes
+through torch autograd with the same render op.  Under torch.distributed the projector
 angles are sharded across ranks: each rank renders its angles, the partial
 dose is all-reduced (RCCL), the adjoint is rank-local and L-BFGS dots are
 all-reduced scalars.
@@ -38,7 +39,7 @@ from .engine import derive_seed_grad
 from .geometry import geometries
 from .integrators import VolumeIntegrator
 from .lbfgs import DirectionPipeline, FusedLinearLBFGS, LinearLBFGS
-from .loss import losses, ThresholdedLoss
+from .loss import losses, L2Loss, ThresholdedLoss
 from .optimizers import Adam, SGD
 from .scene import load_dict
 from .utils import discretize, analytic_target, mesh_bbox, target_transform, save_vol, save_img, save_histogram
@@ -508,8 +509,11 @@ class TvamProblem(ShardedLoop):
             raise ValueError(f"Unknown loss type: '{ltype}'. Available losses are: {list(losses.keys())}")
         self.loss_fn = losses[ltype](lcfg)
         lf = self.loss_fn
-        fusable = (isinstance(lf, ThresholdedLoss) and dev.type == 'cuda' and float(lf.K).is_integer()
-                   and 1 <= int(lf.K) <= 16)
+        # a loss with a HIP kernel: ThresholdedLoss with an integer K, L2Loss; over a one-channel or a
+        # surface-aware (two-channel) target.  Config 'fused_loss': false forces the torch path
+        has_kernel = (isinstance(lf, L2Loss) or
+                      (isinstance(lf, ThresholdedLoss) and float(lf.K).is_integer() and 1 <= int(lf.K) <= 16))
+        fusable = has_kernel and dev.type == 'cuda' and bool(config.get('fused_loss', True))
 
         # Sharding.  'angle': contiguous angle blocks, the
         # partial doses are all-reduced.  'slab': planar rays (regular sampling)
@@ -575,7 +579,7 @@ class TvamProblem(ShardedLoop):
         planar = self.regular_sampling and full_desc.albedo == 0.0 and not self.surface_aware and not cone
         if shard == 'slab' and not (planar and fusable):
             raise ValueError("z-slab sharding needs regular sampling, a non-scattering medium and the fused "
-                             "thresholded loss")
+                             "thresholded loss (an integer K) or the fused l2 loss")
         self.shard = 'slab' if (shard == 'slab' or (shard == 'auto' and self.world > 1 and planar
                                                      and fusable)) else 'angle'
         self.n_vox = int(full_desc.film_res[0]) * int(full_desc.film_res[1]) * self.res_z
@@ -614,7 +618,7 @@ class TvamProblem(ShardedLoop):
             self._filter_radon(config)
         if 'filter_corner' in config and filter_pixels:
             self._filter_corner(config)
-        self.fused = fusable and self.target.shape[-1] == 1
+        self.fused = fusable and self.target.shape[-1] in (1, 2)
         self.grad_vol = torch.empty(self.proj.film_shape, dtype=torch.float32, device=dev)
         self.opt = None
         self.loss_hist = []

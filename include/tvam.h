@@ -28,6 +28,8 @@
  *                         LinearLBFGS.step lbfgs.py:256-266)
  *   tvam_loss_threshold_probes <- the same Armijo probes, up to 8 step sizes per pass
  *                         (lbfgs.py:255-268: one loss pass and one host read per batch)
+ *   tvam_loss_square, tvam_loss_surface (+ _probes) <- L2Loss.__call__ loss.py:62-79 and both
+ *                         losses over a surface-aware target, loss.py:39-47 (fused the same way)
  *   tvam_plan_destroy, tvam_last_error  <- Python exception plumbing
  *
  * All buffers are caller-owned device pointers (e.g. torch tensors' data_ptr()).
@@ -655,6 +657,55 @@ int tvam_loss_threshold_probes_mask(const float* dose, const float* ddose,
                                     int32_t K, float tl, float tu, float w_object,
                                     float w_void, float w_limit, float scale,
                                     double* out, void* hip_stream);
+
+/*
+ * L2Loss over a one-channel target, and ThresholdedLoss / L2Loss over a surface-aware (two-channel)
+ * film, fused (loss.py:28-59, :62-79, :82-132).  (Added to ABI v13: no struct or existing signature
+ * changed.)  x = dose + alpha * ddose as one fmaf (ddose may be NULL in the value entries);
+ * out[0] += scale * sum of the per-voxel elements (f64 accumulation, the caller zeroes out); grad (may
+ * be NULL) = dL/dx per float, times scale (scale = 1 / voxels of the whole film for 'mean', the
+ * caller's to supply: the reduction counts voxels, not floats).  Any 4-byte alignment; float4
+ * accesses when every pointer is 16-byte aligned.  Per element, fp32 operations in this order,
+ * none contracted:
+ *
+ *   tvam_loss_square: n floats each.  d = x - target; element d * d; grad = (2 * d) * scale.  target
+ *   is the greyscale f32 target itself (no bit mask).
+ *
+ *   tvam_loss_surface: dose, ddose, target, grad hold 2 * n_vox floats, interleaved per voxel: x0, x1
+ *   (dose inside / outside the object) and t0 = V_in, t1 = V_out.  s = t0 + t1, w_in = t0 / s, w_out =
+ *   t1 / s (IEEE divisions; a voxel with s = 0 is outside the contract, 0 / 0 as in the reference).
+ *   element = w_in * e_in + w_out * e_out; grad[2 i] = (w_in * g_in) * scale, grad[2 i + 1] = (w_out *
+ *   g_out) * scale, with
+ *     kind TVAM_LOSS_KIND_THRESHOLD: e_in = w_object relu(tu - x0)^K + w_limit relu(x0 - 1)^K, e_out =
+ *       w_void relu(x1 - tl)^K and their derivatives as in tvam_loss_threshold (0 at a kink), integer
+ *       K in [1, 16];
+ *     kind TVAM_LOSS_KIND_L2: e_in = (x0 - 1)^2, e_out = x1^2, g_in = 2 (x0 - 1), g_out = 2 x1 (K, tl,
+ *       tu and the weights are ignored).
+ *
+ *   tvam_loss_square_probes / tvam_loss_surface_probes: the values at dose + alphas[j] * ddose for j <
+ *   n_alpha (<= 8, alphas on the host) in one pass, out[j] += the scaled sum (the caller zeroes
+ *   out[0..n_alpha)).  Per element the same arithmetic as the value entry with that alpha.
+ *
+ * TVAM_ERR_INVALID (the message names the entry and the cause): null dose, target or out; for the
+ * probes null ddose or alphas, n_alpha outside [1, 8]; an unknown kind; K outside [1, 16] with the
+ * threshold kind.  n == 0 launches nothing and leaves out untouched.
+ */
+#define TVAM_LOSS_KIND_THRESHOLD 0
+#define TVAM_LOSS_KIND_L2 1
+int tvam_loss_square(const float* dose, const float* ddose, float alpha, const float* target,
+                     uint64_t n, float scale, double* out, float* grad, void* hip_stream);
+int tvam_loss_square_probes(const float* dose, const float* ddose, const float* alphas,
+                            int32_t n_alpha, const float* target, uint64_t n, float scale,
+                            double* out, void* hip_stream);
+int tvam_loss_surface(int32_t kind, const float* dose, const float* ddose, float alpha,
+                      const float* target, uint64_t n_vox, int32_t K, float tl, float tu,
+                      float w_object, float w_void, float w_limit, float scale, double* out,
+                      float* grad, void* hip_stream);
+int tvam_loss_surface_probes(int32_t kind, const float* dose, const float* ddose,
+                             const float* alphas, int32_t n_alpha, const float* target,
+                             uint64_t n_vox, int32_t K, float tl, float tu, float w_object,
+                             float w_void, float w_limit, float scale, double* out,
+                             void* hip_stream);
 
 /*
  * The print report's primitive (drtvam_amd/utils.py: iou_sweep, save_histogram; the reference's
