@@ -192,6 +192,9 @@ EXPORTS = {
     "tvam_plan_destroy": (None, [_P]),
     "tvam_forward": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_adjoint": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
+    "tvam_forward_dsigma": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
+    "tvam_adjoint_dsigma": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
+    "tvam_dsigma_weights": (ctypes.c_int, [ctypes.c_float, _P, _P, ctypes.c_int64, _P]),
     "tvam_forward_slices": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.c_int32, ctypes.c_int32, _P, _P]),
     "tvam_plan_fwd_chunk": (ctypes.c_int, [_P]),
@@ -373,6 +376,22 @@ def traced_segments(desc: TvamDesc, o, d):
     check(load_library().tvam_traced_segments(ctypes.byref(desc), o.ctypes.data, d.ctypes.data, o.shape[0],
                                               segs.ctypes.data))
     return segs
+
+
+def dsigma_weights(sigma_t, T0, dt):
+    """The extinction derivative's visit weight w'(T0, dt) = e^{-s T0} (dt (1 - q) - T0 q), q = 1 - e^{-s dt},
+    on the host in the kernels' own float32 expression (tvam_dsigma_weights): float32, T0's shape (T0 and dt
+    broadcast).  No GPU is touched."""
+    import numpy as np
+    T0, dt = np.broadcast_arrays(np.asarray(T0, dtype=np.float32), np.asarray(dt, dtype=np.float32))
+    shape = T0.shape
+    T0 = np.ascontiguousarray(T0).reshape(-1)
+    dt = np.ascontiguousarray(dt).reshape(-1)
+    w = np.empty(T0.size, np.float32)
+    check(load_library().tvam_dsigma_weights(float(sigma_t), T0.ctypes.data if T0.size else None,
+                                             dt.ctypes.data if dt.size else None, T0.size,
+                                             w.ctypes.data if w.size else None))
+    return w.reshape(shape)
 
 
 def default_desc() -> TvamDesc:

@@ -451,6 +451,67 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     return 0;
 }
 
+// Extinction derivatives (tvam_dsigma.hip).  What both entries refuse, from the descriptor and the
+// plan's flags alone: no device call, nothing allocated.
+static int dsigma_refuse(const tvam_plan* p, const char* who) {
+    const tvam_desc& d = p->desc;
+    const char* why = nullptr;
+    if (d.albedo > 0.0f) why = "albedo > 0 (the free-flight terms of a scattering medium are not built)";
+    else if (d.sensor_type != TVAM_SENSOR_DDA) why = "the 'ratio' / 'delta' sensors are not differentiated";
+    else if (p->surface) why = "a surface-aware (two-channel) film is not differentiated";
+    else if (p->k.z0 != 0 || p->k.nz != p->k.res[2]) why = "a film slab is not differentiated (render the whole film)";
+    else if (d.sample_time) why = "sample_time is not differentiated";
+    else if (p->dbl) why = "a 'double_cylindrical' plan is not differentiated (its second segment starts at the first one's path length)";
+    return why ? tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": " + why) : 0;
+}
+
+extern "C" int tvam_forward_dsigma(tvam_plan* p, const float* active_data, const uint32_t* active_pixels,
+                                   uint64_t n_active, uint32_t spp, uint32_t seed, float* tangent, void* stream_) {
+    if (!p || !tangent || (!active_data && n_active)) return tvam_fail(TVAM_ERR_INVALID, "tvam_forward_dsigma: null argument");
+    int rc = dsigma_refuse(p, "tvam_forward_dsigma");
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    TvamConsts k;
+    if ((rc = call_setup(p, n_active, active_pixels, spp, k))) return rc;
+    const size_t V = (size_t)k.res[0] * k.res[1] * k.nz;
+    hipError_t e = hipMemsetAsync(tangent, 0, V * sizeof(float), stream);
+    if (e != hipSuccess) return tvam_hip_fail(e, "hipMemsetAsync");
+    if (p->empty || n_active == 0) return 0;
+    const float* pat = active_data;
+    const int32_t* idxmap = nullptr;
+    if ((rc = bind_active(p, k, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
+    e = tvam_launch_dsigma(TVAM_MODE_FWD, p->cone, k, call_tiles(p, spp, seed), pat, idxmap, nullptr, tangent, nullptr,
+                           nullptr, stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "extinction tangent launch");
+}
+
+extern "C" int tvam_adjoint_dsigma(tvam_plan* p, const float* active_data, const float* grad_dose,
+                                   const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                                   double* g_sigma, void* stream_) {
+    if (!p || !grad_dose || !g_sigma || (!active_data && n_active))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_adjoint_dsigma: null argument");
+    int rc = dsigma_refuse(p, "tvam_adjoint_dsigma");
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    TvamConsts k;
+    if ((rc = call_setup(p, n_active, active_pixels, spp, k))) return rc;
+    hipError_t e;
+    if (p->empty || n_active == 0) {
+        e = hipMemsetAsync(g_sigma, 0, sizeof(double), stream);
+        return e == hipSuccess ? 0 : tvam_hip_fail(e, "hipMemsetAsync");
+    }
+    const float* pat = active_data;
+    const int32_t* idxmap = nullptr;
+    if ((rc = bind_active(p, k, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
+    const TvamTiles t = call_tiles(p, spp, seed);
+    // (the grid, and with it the order of the sum, depends on the ray count alone)
+    if ((e = p->dsig_part.grow(tvam_dsigma_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp))) != hipSuccess)
+        return tvam_hip_fail(e, "hipMalloc (extinction partials)");
+    e = tvam_launch_dsigma(TVAM_MODE_ADJ, p->cone, k, t, pat, idxmap, grad_dose, nullptr, p->dsig_part.get(), g_sigma,
+                           stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "extinction gradient launch");
+}
+
 // The rays of a call (tvam_cone.hip's ray generation serves every projector kind); `segs`: both
 // medium segments of a 'double_cylindrical' plan instead (tvam_plan_segments).
 static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,

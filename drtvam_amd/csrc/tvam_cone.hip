@@ -142,15 +142,6 @@ __global__ __launch_bounds__(256) void tvam_cone_export_kernel(TvamConsts k, Tva
 
 }  // namespace
 
-// MESH of a launch and its dynamic LDS.
-static int cn_mesh_mode(const TvamConsts& k) {
-    // (a glass vial reaches these kernels only through a traced plan: tvam_plan_create's plans of
-    // such a vial are planar)
-    if (k.vial_type == TVAM_VIAL_CYLINDRICAL || k.vial_type == TVAM_VIAL_SQUARE) return CN_GLASS;
-    return k.vial_type != TVAM_VIAL_CUSTOM ? CN_NO_MESH : (k.mesh.lds_bytes > 0 ? CN_MESH_LDS : CN_MESH_GLOBAL);
-}
-static size_t cn_lds(const TvamConsts& k) { return cn_mesh_mode(k) == CN_MESH_LDS ? cn_mesh_lds_bytes(k.mesh) : 0; }
-
 template <int MESH>
 static void cn_launch_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
                            const float* gin, float* out, unsigned long long* counter, hipStream_t stream) {

@@ -50,6 +50,15 @@ inline size_t cn_mesh_lds_bytes(const TvamMesh& m) {
     return sizeof(float4) * ((size_t)2 * m.n_nodes + (9 * (size_t)m.n_tris + 3) / 4 + ((size_t)m.n_tris + 3) / 4);
 }
 
+// MESH of a launch over a 3-D ray plan and its dynamic LDS.
+inline int cn_mesh_mode(const TvamConsts& k) {
+    // (a glass vial reaches these kernels only through a traced plan: tvam_plan_create's plans of
+    // such a vial are planar)
+    if (k.vial_type == TVAM_VIAL_CYLINDRICAL || k.vial_type == TVAM_VIAL_SQUARE) return CN_GLASS;
+    return k.vial_type != TVAM_VIAL_CUSTOM ? CN_NO_MESH : (k.mesh.lds_bytes > 0 ? CN_MESH_LDS : CN_MESH_GLOBAL);
+}
+inline size_t cn_lds(const TvamConsts& k) { return cn_mesh_mode(k) == CN_MESH_LDS ? cn_mesh_lds_bytes(k.mesh) : 0; }
+
 #ifndef TVAM_MESH_BRUTE
 #define TVAM_MESH_BRUTE 0  // 1: a measurement build whose kernels loop over every triangle
 #endif
@@ -173,11 +182,12 @@ __device__ __forceinline__ void cn_projector_ray(const TvamConsts& k, const Tvam
 // box clip, start / end voxel, dtmax / tstep per axis, then per visit dt = min(dtmax, remaining),
 // dtmax -= dt (an axis at its crossing restarts from tstep), so a ray visits exactly the oracle's
 // voxels (sc_dda's closed-form crossing times fmaf(n, ts, dtm0) can split a near-tie the other
-// way).  The visit weight e^{-st t} (1 - e^{-st dt}) without cancellation (tvam_omexp).  FWD adds
-// em * weight into dose, ADJ returns sum weight * grad * inv_vol, COUNT counts visits.
-template <int MODE>
-__device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], const float d[3], float maxt, float em,
-                                        float* __restrict__ dose, const float* __restrict__ gin, uint64_t& nvis) {
+// way).  cn_dda_steps is the stepping alone, shared by cn_dda and the extinction derivative
+// (tvam_dsigma.hip): visit(film index, t, dt) per voxel visit, t the in-medium path length from o
+// at which the visit starts.
+template <typename F>
+__device__ __forceinline__ void cn_dda_steps(const TvamConsts& k, const float o[3], const float d[3], float maxt,
+                                             F&& visit) {
     float lo[3], hi[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -188,7 +198,7 @@ __device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], c
     }
     const float t_start = fmaxf(fmaxf(fmaxf(fmaxf(lo[0], lo[1]), lo[2]), 0.0f), 0.0f);
     const float t_end = fminf(fminf(fminf(hi[0], hi[1]), hi[2]), maxt);
-    if (!(isfinite(t_start) && isfinite(t_end) && t_start < t_end)) return 0.0f;
+    if (!(isfinite(t_start) && isfinite(t_end) && t_start < t_end)) return;
     // axes in scalars (dynamically indexed arrays would be promoted to scratch)
     int cur[3], endv[3], step[3];
     float dtm[3], ts[3];
@@ -211,19 +221,14 @@ __device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], c
         ts[a] = valid ? (k.h[a] / d[a]) * (float)step[a] : TVAM_INF;
     }
     const int64_t sy = k.res[0], sz = (int64_t)k.res[0] * k.res[1];
-    float t = t_start, remaining = t_end - t_start, acc = 0.0f;
+    float t = t_start, remaining = t_end - t_start;
     // a ray steps at most res - 1 times per axis (the guard only bounds the loop)
     const int nmax = k.res[0] + k.res[1] + k.res[2] + 1;
     for (int it = 0; it < nmax; ++it) {
         const float dt = fminf(fminf(fminf(dtm[0], dtm[1]), dtm[2]), remaining);
         remaining = remaining - dt;
         const int64_t idx = cur[0] + cur[1] * sy + cur[2] * sz;
-        if (MODE != TVAM_MODE_COUNT) {
-            const float c = sc_exp2(k.nsig2 * t) * tvam_omexp(k.sig_t * fmaxf(dt, 0.0f));
-            if (MODE == TVAM_MODE_FWD) atomicAdd(&dose[idx], em * c);
-            else acc = fmaf(c, gin[idx] * k.inv_vol, acc);
-        }
-        ++nvis;
+        visit(idx, t, dt);
         const bool alive = (cur[0] != endv[0] || cur[1] != endv[1] || cur[2] != endv[2]) && remaining > 1e-6f;
         if (!alive) break;
 #pragma unroll
@@ -236,6 +241,22 @@ __device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], c
             break;
         t = t + dt;
     }
+}
+
+// The visit weight e^{-st t} (1 - e^{-st dt}) without cancellation (tvam_omexp).  FWD adds
+// em * weight into dose, ADJ returns sum weight * grad * inv_vol, COUNT counts visits.
+template <int MODE>
+__device__ __forceinline__ float cn_dda(const TvamConsts& k, const float o[3], const float d[3], float maxt, float em,
+                                        float* __restrict__ dose, const float* __restrict__ gin, uint64_t& nvis) {
+    float acc = 0.0f;
+    cn_dda_steps(k, o, d, maxt, [&](int64_t idx, float t, float dt) {
+        if (MODE != TVAM_MODE_COUNT) {
+            const float c = sc_exp2(k.nsig2 * t) * tvam_omexp(k.sig_t * fmaxf(dt, 0.0f));
+            if (MODE == TVAM_MODE_FWD) atomicAdd(&dose[idx], em * c);
+            else acc = fmaf(c, gin[idx] * k.inv_vol, acc);
+        }
+        ++nvis;
+    });
     return acc;
 }
 

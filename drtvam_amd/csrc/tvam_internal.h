@@ -320,6 +320,15 @@ void tvam_double_write_records(const TvamConsts& k, const TvamTiles& t, const fl
                                const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
 hipError_t tvam_launch_double_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
                                      float* segs, hipStream_t stream);
+// Extinction derivatives (tvam_dsigma.hip): one thread per (ray, sample) over the segment the plan's
+// forward marches (cone: a 3-D ray plan's cn_ray_at, else the collimated plans' planar first
+// segment).  FWD: the tangent film d dose / d sigma_t added into `tangent` (zeroed by the caller).
+// ADJ: sum_v gin[v] * tangent[v] into g_sigma[0] (device, overwritten) through `partials`, one fp64
+// partial per workgroup of the launch's grid (tvam_dsigma_grid of the ray count); no atomics.
+unsigned tvam_dsigma_grid(int64_t n_rays);
+hipError_t tvam_launch_dsigma(int mode, bool cone, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                              const int32_t* idxmap, const float* gin, float* tangent, double* partials,
+                              double* g_sigma, hipStream_t stream);
 hipError_t tvam_launch_scale_volumes(int64_t n, const float* vols, float* dose, hipStream_t stream);
 // compute_volume (sensor.py:47-110): volumes [res z][y][x][2]
 hipError_t tvam_launch_volumes(const TvamConsts& k, uint32_t sample_count, float* volumes, hipStream_t stream);

@@ -153,6 +153,39 @@ class Projection:
                 n_active, spp, seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
         return out
 
+    def forward_dsigma(self, active_data: torch.Tensor, active_pixels: Optional[torch.Tensor] = None, spp: int = 1,
+                       seed: int = 0) -> torch.Tensor:
+        """The tangent film d dose / d sigma_t of forward(active_data, ...) (tvam_forward_dsigma), film
+        shaped.  Non-scattering media; ValueError names what the entry refuses."""
+        self._check_tensor(active_data, torch.float32, "active_data")
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+        out = torch.empty(self.film_shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_forward_dsigma(
+                self._plan, active_data.data_ptr(), None if active_pixels is None else active_pixels.data_ptr(),
+                active_data.numel(), spp, seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    def adjoint_dsigma(self, active_data: torch.Tensor, grad_dose: torch.Tensor,
+                       active_pixels: Optional[torch.Tensor] = None, spp: int = 1, seed: int = 0) -> torch.Tensor:
+        """d <grad_dose, forward(active_data, ...)> / d sigma_t (tvam_adjoint_dsigma): a 0-dim float64
+        tensor, the same bits for the same call."""
+        self._check_tensor(active_data, torch.float32, "active_data")
+        grad_dose = grad_dose.contiguous()
+        self._check_tensor(grad_dose, torch.float32, "grad_dose")
+        if grad_dose.numel() != self.film_shape[0] * self.film_shape[1] * self.film_shape[2] * self.film_shape[3]:
+            raise ValueError("grad_dose has the wrong number of elements")
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+        out = torch.empty((), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_adjoint_dsigma(
+                self._plan, active_data.data_ptr(), grad_dose.data_ptr(),
+                None if active_pixels is None else active_pixels.data_ptr(), active_data.numel(), spp,
+                seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
     def adjoint_slices(self, grad_dose: torch.Tensor, n_active: int, z_begin: int, z_end: int, row_begin: int,
                        row_end: int, out: torch.Tensor) -> torch.Tensor:
         """The planar adjoint of film slices [z_begin, z_end) into DMD rows [row_begin, row_end) of every
@@ -370,29 +403,52 @@ class Projection:
 
 
 class TvamRender(torch.autograd.Function):
-    """dose = render(active_data); d loss / d active_data via the adjoint kernel."""
+    """dose = render(active_data); d loss / d active_data via the adjoint kernel, and d loss / d sigma_t
+    via the extinction-gradient kernel when the medium's sigma_t is an input that requires grad."""
 
     @staticmethod
     def forward(ctx, active_data, proj: Projection, active_pixels, spp: int, spp_grad: int, seed: int,
-                seed_grad: int):
+                seed_grad: int, sigma_t=None):
         ctx.proj = proj
         ctx.active_pixels = active_pixels
         ctx.spp_grad = spp_grad
         ctx.seed_grad = seed_grad
         ctx.n_active = active_data.numel()
-        return proj.forward(active_data.detach().contiguous(), active_pixels, spp, seed)
+        data = active_data.detach().contiguous()
+        if sigma_t is not None and sigma_t.requires_grad:  # the sigma gradient renders the patterns again
+            ctx.save_for_backward(data)
+            ctx.sigma_like = (sigma_t.device, sigma_t.dtype)
+        return proj.forward(data, active_pixels, spp, seed)
 
     @staticmethod
     def backward(ctx, grad_dose):
-        g = ctx.proj.adjoint(grad_dose.contiguous(), ctx.n_active, ctx.active_pixels, ctx.spp_grad, ctx.seed_grad)
-        return g, None, None, None, None, None, None
+        grad_dose = grad_dose.contiguous()
+        g = None
+        if ctx.needs_input_grad[0]:
+            g = ctx.proj.adjoint(grad_dose, ctx.n_active, ctx.active_pixels, ctx.spp_grad, ctx.seed_grad)
+        gs = None
+        if ctx.needs_input_grad[7]:
+            (data,) = ctx.saved_tensors
+            gs = ctx.proj.adjoint_dsigma(data, grad_dose, ctx.active_pixels, ctx.spp_grad, ctx.seed_grad)
+            gs = gs.to(device=ctx.sigma_like[0], dtype=ctx.sigma_like[1])
+        return g, None, None, None, None, None, None, gs
 
 
 def render(proj: Projection, active_data: torch.Tensor, active_pixels: Optional[torch.Tensor] = None,
-           spp: int = 1, spp_grad: Optional[int] = None, seed: int = 0, seed_grad: Optional[int] = None):
+           spp: int = 1, spp_grad: Optional[int] = None, seed: int = 0, seed_grad: Optional[int] = None,
+           sigma_t: Optional[torch.Tensor] = None):
+    """sigma_t: the medium's extinction as a 0-dim tensor, an input of the render when it requires
+    grad.  The plan bakes sigma_t in, so the tensor must hold the plan's own value (as float32)."""
     spp_grad = spp if spp_grad is None else spp_grad
     seed_grad = derive_seed_grad(seed) if seed_grad is None else seed_grad
-    return TvamRender.apply(active_data, proj, active_pixels, spp, spp_grad, seed, seed_grad)
+    if sigma_t is not None:
+        if sigma_t.dim() != 0:
+            raise ValueError("render: sigma_t must be a 0-dim tensor")
+        have = ctypes.c_float(float(sigma_t.detach())).value
+        if have != ctypes.c_float(proj.desc.sigma_t).value:
+            raise ValueError(f"render: sigma_t = {have!r} is not the plan's extinction {proj.desc.sigma_t!r}; "
+                             "build the Projection from a descriptor with this sigma_t")
+    return TvamRender.apply(active_data, proj, active_pixels, spp, spp_grad, seed, seed_grad, sigma_t)
 
 
 def target_mask(target: torch.Tensor) -> torch.Tensor:

@@ -30,6 +30,7 @@ class TVAMIntegrator:
         self.tile = props.get('tile', 0)
         self.flags = props.get('flags', 0)
         self._plans = {}
+        self._families = {}  # descriptor with sigma_t blanked -> its one key in _plans
 
     def parse_scene(self, scene):
         if scene.container is None:
@@ -74,10 +75,19 @@ class TVAMIntegrator:
         key = (bytes(memoryview(ctypes.string_at(ctypes.addressof(d), ctypes.sizeof(d)))), d.traced_vial, str(dev))
         proj = self._plans.get(key)
         if proj is None:
+            # a fit of the extinction builds a plan per step: plans whose descriptors differ in
+            # sigma_t alone evict one another
+            fam = d.copy()
+            fam.sigma_t = 0.0
+            fam = (bytes(memoryview(ctypes.string_at(ctypes.addressof(fam), ctypes.sizeof(fam)))), d.traced_vial, str(dev))
+            old = self._families.pop(fam, None)
+            if old is not None:
+                self._plans.pop(old).close()
             proj = Projection(d, dev)
             if sensor.film().surface_aware:  # inv_vol of the two channels (volume.py:41-42)
                 proj.set_volumes(sensor.compute_volume(scene).to(dev))
             self._plans[key] = proj
+            self._families[fam] = key
         return proj
 
     def prepare(self, projector, seed: int = 0, spp: int = 0):

@@ -15,6 +15,11 @@ from .common import TVAMIntegrator
 from ..engine import derive_seed_grad, render as engine_render
 
 
+def _sigma_param(scene):
+    """The medium's extinction as traverse(scene) exposes it ('printing_medium.sigma_t'), or None."""
+    return getattr(scene, 'sigma_t_param', None)
+
+
 def _check_projectors(scene):
     if scene.projector is None:
         raise Exception("No projector found in the scene")
@@ -55,7 +60,8 @@ class VolumeIntegrator(TVAMIntegrator):
 
     def render_differentiable(self, scene, sensor=0, spp: int = 0, spp_grad: Optional[int] = None, seed: int = 0,
                               seed_grad: Optional[int] = None, active_data: Optional[torch.Tensor] = None):
-        """mi.render with AD: dose depends differentiably on active_data (default: projector.active_data)."""
+        """mi.render with AD: dose depends differentiably on active_data (default: projector.active_data)
+        and, when traverse(scene)'s 'printing_medium.sigma_t' requires grad, on the medium's extinction."""
         _check_projectors(scene)
         sensor = self._sensor(scene, sensor)
         projector = scene.projector
@@ -64,29 +70,44 @@ class VolumeIntegrator(TVAMIntegrator):
         proj = self.projection(scene, sensor)
         pix = None if projector.dense else projector.active_pixels
         x = projector.active_data if active_data is None else active_data
-        return engine_render(proj, x, pix, spp, spp_grad, seed, derive_seed_grad(seed) if seed_grad is None else seed_grad)
+        sig = _sigma_param(scene)
+        if sig is not None and not sig.requires_grad:
+            sig = None
+        return engine_render(proj, x, pix, spp, spp_grad, seed, derive_seed_grad(seed) if seed_grad is None else seed_grad,
+                             sigma_t=sig)
 
     def render_forward(self, scene, params=None, sensor=0, seed: int = 0, spp: int = 0,
-                       tangent: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       tangent: Optional[torch.Tensor] = None,
+                       tangent_sigma_t: Optional[float] = None) -> torch.Tensor:
         """Forward-mode derivative (volume.py:58-95): the dose tangent [Z, Y, X, C] produced by a
         tangent of projector.active_data.  The render is linear in the patterns, so this is the
         forward projection of the tangent (the reference propagates dr.grad(active_data) through
         Le in ADMode.Forward and scales by inv_vol, as the forward kernel does).  `tangent`
-        defaults to projector.active_data.grad, the slot the reference reads it from."""
+        defaults to projector.active_data.grad, the slot the reference reads it from.
+        `tangent_sigma_t`: a tangent of the medium's extinction (sensor.py:371-375); the result is
+        A tangent + tangent_sigma_t T with T = d dose / d sigma_t of projector.active_data
+        (Projection.forward_dsigma).  Either tangent alone is allowed."""
         _check_projectors(scene)
         sensor = self._sensor(scene, sensor)
         projector = scene.projector
         if tangent is None:
             tangent = projector.active_data.grad
-        if tangent is None:
+        if tangent is None and tangent_sigma_t is None:
             raise ValueError("render_forward: no tangent (set projector.active_data.grad or pass `tangent`)")
-        if tangent.numel() != projector.active_size():
+        if tangent is not None and tangent.numel() != projector.active_size():
             raise ValueError("render_forward: the tangent must have one entry per active pixel")
         seed, spp = self.prepare(projector, seed, spp)
         proj = self.projection(scene, sensor)
         pix = None if projector.dense else projector.active_pixels
         with torch.no_grad():
-            return proj.forward(tangent.detach().to(dtype=torch.float32).contiguous(), pix, spp, seed)
+            out = None
+            if tangent is not None:
+                out = proj.forward(tangent.detach().to(dtype=torch.float32).contiguous(), pix, spp, seed)
+            if tangent_sigma_t is not None:
+                T = proj.forward_dsigma(projector.active_data.detach().contiguous(), pix, spp, seed)
+                T *= float(tangent_sigma_t)
+                out = T if out is None else out.add_(T)
+            return out
 
     def render_backward(self, scene, params, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
         _check_projectors(scene)
@@ -101,6 +122,14 @@ class VolumeIntegrator(TVAMIntegrator):
             x.grad = g
         else:
             x.grad += g
+        sig = _sigma_param(scene)
+        if sig is not None and sig.requires_grad:  # st_grad into sigma_t (volume.py:274-280)
+            gs = proj.adjoint_dsigma(x.detach().contiguous(), grad_in.contiguous(), pix, spp, seed)
+            gs = gs.to(device=sig.device, dtype=sig.dtype)
+            if sig.grad is None:
+                sig.grad = gs
+            else:
+                sig.grad += gs
 
 
 integrators = {'volume': VolumeIntegrator}

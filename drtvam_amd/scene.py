@@ -28,6 +28,7 @@ class Scene:
         self.target = None
         self.integrator = None
         self.shapes = {}
+        self.sigma_t_param = None  # traverse()'s 'printing_medium.sigma_t', once traversed
 
     def emitters(self):
         return [self.projector] if self.projector is not None else []
@@ -135,7 +136,9 @@ def load_dict(scene_dict: dict) -> Scene:
 
 
 class SceneParameters(dict):
-    """``mi.traverse(scene)`` equivalent for the differentiable projector data."""
+    """``mi.traverse(scene)`` equivalent for the differentiable projector data and the printing
+    medium's extinction ('printing_medium.sigma_t': a 0-dim float32 tensor on the host holding the
+    container's value; ``update`` writes it back, so the next plan is built with it)."""
 
     def __init__(self, scene: Scene):
         super().__init__()
@@ -143,13 +146,26 @@ class SceneParameters(dict):
         p = scene.projector
         dict.__setitem__(self, 'projector.active_data', p.active_data)
         dict.__setitem__(self, 'projector.active_pixels', p.active_pixels)
+        if scene.container is not None:
+            sig = torch.tensor(float(scene.container.sigma_t), dtype=torch.float32)
+            dict.__setitem__(self, 'printing_medium.sigma_t', sig)
+            scene.sigma_t_param = sig
 
     def update(self, values=None):
         if values is not None:
-            for k in ('projector.active_data', 'projector.active_pixels'):
+            for k in ('projector.active_data', 'projector.active_pixels', 'printing_medium.sigma_t'):
                 if k in values:
                     dict.__setitem__(self, k, values[k])
         self.scene.projector.set_active(self['projector.active_data'], self['projector.active_pixels'])
+        sig = self.get('printing_medium.sigma_t')
+        if sig is not None:
+            if not isinstance(sig, torch.Tensor):
+                sig = torch.tensor(float(sig), dtype=torch.float32)
+                dict.__setitem__(self, 'printing_medium.sigma_t', sig)
+            if sig.dim() != 0:
+                raise ValueError("'printing_medium.sigma_t' must be a 0-dim tensor")
+            self.scene.container.sigma_t = float(sig.detach().to(torch.float32))
+            self.scene.sigma_t_param = sig
 
 
 def traverse(scene: Scene) -> SceneParameters:
@@ -158,10 +174,12 @@ def traverse(scene: Scene) -> SceneParameters:
 
 def render(scene: Scene, params=None, integrator=None, sensor=0, spp: int = 0, spp_grad: int = 0, seed: int = 0,
            seed_grad: Optional[int] = None) -> torch.Tensor:
-    """Differentiable render (``mi.render``): gradients flow to projector.active_data when it requires grad."""
+    """Differentiable render (``mi.render``): gradients flow to projector.active_data, and to
+    traverse(scene)'s 'printing_medium.sigma_t', when they require grad."""
     integrator = integrator or scene.integrator
     x = scene.projector.active_data
-    if x.requires_grad and torch.is_grad_enabled():
+    sig = getattr(scene, 'sigma_t_param', None)
+    if (x.requires_grad or (sig is not None and sig.requires_grad)) and torch.is_grad_enabled():
         return integrator.render_differentiable(scene, sensor, spp=spp, spp_grad=spp_grad or None, seed=seed,
                                                 seed_grad=seed_grad)
     return integrator.render(scene, sensor, seed=seed, spp=spp)

@@ -22,6 +22,9 @@
  *   tvam_adjoint       <- VolumeIntegrator.render_backward integrators/volume.py:97-134
  *                         (+ accumulate backward branch sensor.py:417-423 and
  *                         dr.backward_from(Le * em_grad) volume.py:274-276)
+ *   tvam_forward_dsigma, tvam_adjoint_dsigma <- the medium derivative of the same march: the
+ *                         sigma_t tangent of render_forward (volume.py:58-95, sensor.py:371-375) and
+ *                         st_grad of accumulate sent into sigma_t (sensor.py:377-440, volume.py:274-280)
  *   tvam_count_visits  <- (new) exact DDA visit count H used for the roofline
  *   tvam_loss_threshold<- ThresholdedLoss.__call__ loss.py:28-59, :119-132 (fused
  *                         value + dL/dx, also used for the Armijo probes of
@@ -343,6 +346,38 @@ int tvam_adjoint(tvam_plan* plan, const float* grad_dose,
                  const uint32_t* active_pixels, uint64_t n_active,
                  uint32_t spp, uint32_t seed, float* grad_active,
                  void* hip_stream);
+
+/*
+ * Extinction derivatives: d dose / d sigma_t of a non-scattering medium in forward and reverse mode,
+ * the reference's g_st (DDAVolumetricSensor.accumulate sensor.py:377-440, sent into sigma_t by
+ * volume.py:274-280; forward mode sensor.py:371-375, volume.py:58-95).  (Added to ABI v13: no struct
+ * or existing signature changed.)  With albedo = 0 only the visit weight depends on sigma_t: a visit
+ * that starts at in-medium path length T0 (from the segment origin) and lasts dt deposits
+ * e^{-s T0} - e^{-s (T0 + dt)}, whose derivative is
+ *   w'(T0, dt) = e^{-s T0} (dt (1 - q) - T0 q),  q = 1 - e^{-s dt}.
+ *
+ *   tvam_forward_dsigma: tangent (device, f32, the dose's layout, overwritten) = the forward render of
+ *     active_data with w' in place of the visit weight: T[v] = d dose[v] / d sigma_t.
+ *   tvam_adjoint_dsigma: g_sigma[0] (device, f64, overwritten) = sum_v grad_dose[v] T[v], the gradient
+ *     of <grad_dose, tvam_forward(active_data)> in sigma_t.  Per ray a gather in f32, the rays summed in
+ *     f64 in an order that depends on the ray count alone: no float atomics, identical calls give
+ *     identical bits.
+ *   active_data, active_pixels, n_active, spp, seed as in tvam_forward (angle shards, crops, sparse
+ *   sets, jittered sampling with the plan's own sampler streams).  Asynchronous on hip_stream.  Both
+ *   march every ray's first medium segment with the reference's DDA stepping, whichever forward the
+ *   plan picked (planar, ray-driven, tile or 3-D per-ray).
+ *   TVAM_ERR_UNSUPPORTED, the message starting "tvam_forward_dsigma: " / "tvam_adjoint_dsigma: " and
+ *   naming the cause, checked before any device call: albedo > 0, the ratio / delta sensors, a
+ *   surface-aware film, a film slab, sample_time, a 'double_cylindrical' plan.
+ *   tvam_dsigma_weights: w[i] = w'(T0[i], dt[i]) at sigma_t on the host (n entries each), with the
+ *     kernels' own expression in f32.  No GPU is touched.
+ */
+int tvam_forward_dsigma(tvam_plan* plan, const float* active_data, const uint32_t* active_pixels,
+                        uint64_t n_active, uint32_t spp, uint32_t seed, float* tangent, void* hip_stream);
+int tvam_adjoint_dsigma(tvam_plan* plan, const float* active_data, const float* grad_dose,
+                        const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                        double* g_sigma /* device, overwritten */, void* hip_stream);
+int tvam_dsigma_weights(float sigma_t, const float* T0, const float* dt, int64_t n, float* w);
 
 /* Update desc.active_base / desc.active_total of a plan (after the active set was
    compacted, e.g. by 'filter_radon', optimize.py:143-163); later calls seed and
