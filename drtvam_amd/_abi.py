@@ -60,6 +60,16 @@ class TvamDoubleVial(ctypes.Structure):
     ]
 
 
+class TvamInsert(ctypes.Structure):
+    """tvam_insert: one dielectric occluder, its triangles (host) and the BSDF's IORs."""
+    _fields_ = [
+        ("tris", ctypes.c_void_p),
+        ("n_tris", ctypes.c_int32),
+        ("int_ior", ctypes.c_float),
+        ("ext_ior", ctypes.c_float),
+    ]
+
+
 class TvamDesc(ctypes.Structure):
     _fields_ = [
         ("abi_version", ctypes.c_int32),
@@ -118,7 +128,8 @@ class TvamDesc(ctypes.Structure):
         d = TvamDesc()
         ctypes.pointer(d)[0] = self
         # the triangle arrays and the double vial go with the copy
-        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner", "_double_vial", "_traced_vial"):
+        for keep in ("_occluders", "_targets", "_vial_outer", "_vial_inner", "_double_vial", "_traced_vial",
+                     "_inserts"):
             if hasattr(self, keep):
                 setattr(d, keep, getattr(self, keep))
         return d
@@ -162,6 +173,18 @@ class TvamDesc(ctypes.Structure):
         planar kernels).  The mark is not part of the C struct."""
         self._traced_vial = bool(traced)
 
+    def set_inserts(self, inserts) -> None:
+        """Dielectric occluders inside the resin: a sequence of (tris [n][3][3], int_ior, ext_ior), world
+        space, wound outwards.  They are not part of the C struct: engine.Projection hands them to
+        tvam_plan_create_inserts."""
+        import numpy as np
+        self._inserts = [(np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 3, 3), float(ni), float(ne))
+                         for t, ni, ne in inserts]
+
+    @property
+    def inserts(self) -> list:
+        return list(getattr(self, "_inserts", []))
+
     @property
     def traced_vial(self) -> bool:
         return bool(getattr(self, "_traced_vial", False))
@@ -186,6 +209,12 @@ EXPORTS = {
                                                ctypes.POINTER(_P)]),
     "tvam_plan_create_traced": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.c_int, ctypes.POINTER(_P)]),
     "tvam_traced_segments": (ctypes.c_int, [ctypes.POINTER(TvamDesc), _P, _P, ctypes.c_int64, _P]),
+    "tvam_plan_create_inserts": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.POINTER(TvamInsert), ctypes.c_int32,
+                                                ctypes.c_int, ctypes.POINTER(_P)]),
+    "tvam_insert_segments": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.POINTER(TvamInsert), ctypes.c_int32, _P, _P,
+                                            ctypes.c_int64, _P, ctypes.c_int32, _P, _P]),
+    "tvam_plan_insert_segments": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.c_int32, _P, _P, _P]),
     "tvam_plan_segments": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_double_segments": (ctypes.c_int, [ctypes.POINTER(TvamDoubleVial), ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_int32, _P, _P, ctypes.c_int64, _P]),
@@ -376,6 +405,42 @@ def traced_segments(desc: TvamDesc, o, d):
     check(load_library().tvam_traced_segments(ctypes.byref(desc), o.ctypes.data, d.ctypes.data, o.shape[0],
                                               segs.ctypes.data))
     return segs
+
+
+def insert_array(inserts):
+    """The tvam_insert array of a descriptor's inserts (TvamDesc.inserts; the triangle arrays stay theirs),
+    or None when there are none."""
+    if not inserts:
+        return None
+    arr = (TvamInsert * len(inserts))()
+    for i, (t, ni, ne) in enumerate(inserts):
+        arr[i] = TvamInsert(t.ctypes.data if t.size else None, int(t.shape[0]), ni, ne)
+    return arr
+
+
+def insert_segments(desc: TvamDesc, o, d, u=None, max_segments: int = 8):
+    """Medium segments of world rays (o, d: [n, 3]) through the container, black occluders and dielectric
+    inserts of `desc` on the host (tvam_insert_segments, the kernels' own walk): (segs float32
+    [n, max_segments, 8] = o2[0:3], maxt [3], d2[4:7], attenuation [7], zeros past a ray's segments; nseg int32
+    [n]).  u: [n, max_depth, 4], the four draws of each loop iteration, or None: roulette never acts.  No GPU
+    is touched."""
+    import numpy as np
+    o = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("insert_segments: o and d must have the same shape")
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.float32)
+        if u.shape != (o.shape[0], int(desc.max_depth), 4):
+            raise ValueError("insert_segments: u must be [n_rays, max_depth, 4]")
+    ins = desc.inserts
+    arr = insert_array(ins)
+    segs = np.empty((o.shape[0], int(max_segments), 8), np.float32)
+    nseg = np.empty(o.shape[0], np.int32)
+    check(load_library().tvam_insert_segments(ctypes.byref(desc), arr, len(ins), o.ctypes.data, d.ctypes.data,
+                                              o.shape[0], None if u is None else u.ctypes.data, int(max_segments),
+                                              segs.ctypes.data, nseg.ctypes.data))
+    return segs, nseg
 
 
 def dsigma_weights(sigma_t, T0, dt):

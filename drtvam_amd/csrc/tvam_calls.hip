@@ -252,6 +252,7 @@ extern "C" int tvam_forward_slices(tvam_plan* p, const float* active_data, const
                                    uint64_t n_active, uint32_t spp, uint32_t seed, int32_t z_begin, int32_t z_end,
                                    float* dose, void* stream) {
     if (!p) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_forward_slices: dielectric occluders take rays out of their slice (no slice ranges)");
     const int ch = fwd_chunk(p), nz = p->k.nz;
     if (ch == 0) return tvam_fail(TVAM_ERR_UNSUPPORTED, "this plan's forward cannot be split into slice ranges");
     if (z_begin < 0 || z_end > nz || z_begin >= z_end || z_begin % ch != 0 || (z_end % ch != 0 && z_end != nz))
@@ -283,6 +284,10 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
     if ((rc = bind_active(p, kc, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
     if (p->general) {
         TvamTiles t = call_tiles(p, spp, seed);
+        if (p->ins) {  // any number of medium segments per ray: the per-ray atomics alone
+            e = tvam_launch_insert_rays(TVAM_MODE_FWD, kc, t, p->ins_eta.get(), pat, idxmap, nullptr, dose, nullptr, stream);
+            return e == hipSuccess ? 0 : tvam_hip_fail(e, "dielectric-occluder forward launch");
+        }
         if (p->dbl)  // two medium segments per ray: two record slots per path
             return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream, tvam_cone_binned(p),
                                       tvam_double_write_records, tvam_launch_double_rays,
@@ -371,6 +376,7 @@ extern "C" int tvam_adjoint_slices(tvam_plan* p, const float* grad_dose, uint64_
                                    int32_t z_end, int32_t row_begin, int32_t row_end, float* grad_active,
                                    void* stream_) {
     if (!p || !grad_dose || !grad_active) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: dielectric occluders take rays out of their slice (no slice ranges)");
     if (!p->planar || p->general || p->surface || p->desc.albedo != 0.0f || p->empty)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: planar plans only");
     hipStream_t stream = (hipStream_t)stream_;
@@ -418,7 +424,8 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     if (p->general) {
         if (p->empty) return 0;
         TvamTiles t = call_tiles(p, spp, seed);
-        e = p->dbl    ? tvam_launch_double_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+        e = p->ins    ? tvam_launch_insert_rays(TVAM_MODE_ADJ, k, t, p->ins_eta.get(), nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+            : p->dbl  ? tvam_launch_double_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
             : p->cone ? tvam_launch_cone_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
                       : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
         return e == hipSuccess ? 0 : tvam_hip_fail(e, "path adjoint launch");
@@ -462,6 +469,7 @@ static int dsigma_refuse(const tvam_plan* p, const char* who) {
     else if (p->k.z0 != 0 || p->k.nz != p->k.res[2]) why = "a film slab is not differentiated (render the whole film)";
     else if (d.sample_time) why = "sample_time is not differentiated";
     else if (p->dbl) why = "a 'double_cylindrical' plan is not differentiated (its second segment starts at the first one's path length)";
+    else if (p->ins) why = "a plan with dielectric occluders is not differentiated (its later segments start at the earlier ones' path length)";
     return why ? tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": " + why) : 0;
 }
 
@@ -515,7 +523,7 @@ extern "C" int tvam_adjoint_dsigma(tvam_plan* p, const float* active_data, const
 // The rays of a call (tvam_cone.hip's ray generation serves every projector kind); `segs`: both
 // medium segments of a 'double_cylindrical' plan instead (tvam_plan_segments).
 static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
-                       float* rays, float* segs, void* stream_);
+                       float* rays, float* segs, void* stream_, int32_t max_segments = 0, int32_t* nseg = nullptr);
 
 extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                               uint32_t seed, float* rays, void* stream_) {
@@ -523,7 +531,7 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
     const tvam_desc& d = p->desc;
     if ((d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM &&
          d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL && !p->traced) ||
-        d.albedo != 0.0f || d.n_occluder_tris > 0)
+        d.albedo != 0.0f || (d.n_occluder_tris > 0 && !p->ins))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched, 'custom', 'double_cylindrical' and traced glass vial plans without scattering or occluders only");
     return export_rays(p, active_pixels, n_active, spp, seed, rays, nullptr, stream_);
 }
@@ -531,13 +539,24 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
 extern "C" int tvam_plan_segments(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                                   uint32_t seed, float* segs, void* stream_) {
     if (!p || (!segs && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with dielectric occluders has any number of segments per ray (tvam_plan_insert_segments)");
     if (!p->dbl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: 'double_cylindrical' vial plans only");
     if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_segments: segs must be 16-byte aligned");
     return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_);
 }
 
+extern "C" int tvam_plan_insert_segments(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
+                                         uint32_t seed, int32_t max_segments, float* segs, int32_t* nseg,
+                                         void* stream_) {
+    if (!p || ((!segs || !nseg) && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (!p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_insert_segments: plans with dielectric occluders only (tvam_plan_create_inserts)");
+    if (max_segments <= 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_insert_segments: max_segments must be positive");
+    if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_insert_segments: segs must be 16-byte aligned");
+    return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_, max_segments, nseg);
+}
+
 static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
-                       float* rays, float* segs, void* stream_) {
+                       float* rays, float* segs, void* stream_, int32_t max_segments, int32_t* nseg) {
     hipStream_t stream = (hipStream_t)stream_;
     TvamConsts k;
     int rc = call_setup(p, n_active, active_pixels, spp, k);
@@ -547,8 +566,9 @@ static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_a
     const int32_t* idxmap = nullptr;
     if ((rc = bind_active(p, k, nullptr, active_pixels, n_active, stream, nullptr, &idxmap))) return rc;
     TvamTiles t = call_tiles(p, spp, seed);
-    e = p->dbl ? tvam_launch_double_export(k, t, idxmap, rays, segs, stream)
-               : tvam_launch_cone_export(k, t, idxmap, rays, stream);
+    e = p->ins   ? tvam_launch_insert_export(k, t, p->ins_eta.get(), idxmap, rays, segs, max_segments, nseg, stream)
+        : p->dbl ? tvam_launch_double_export(k, t, idxmap, rays, segs, stream)
+                 : tvam_launch_cone_export(k, t, idxmap, rays, stream);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "ray export launch");
 }
 
@@ -563,7 +583,8 @@ extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint
     if (e != hipSuccess) return tvam_hip_fail(e, "hipMemset");
     TvamTiles t = call_tiles(p, spp, seed);
     if (p->general) {
-        e = p->dbl    ? tvam_launch_double_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
+        e = p->ins    ? tvam_launch_insert_rays(TVAM_MODE_COUNT, k, t, p->ins_eta.get(), nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
+            : p->dbl  ? tvam_launch_double_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
             : p->cone ? tvam_launch_cone_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
                       : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
     } else if (p->surface) {
@@ -592,6 +613,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
                           int32_t max_depth, float* radon, void* stream_) {
     if (!p || !radon || n_target_tris < 0 || (n_target_tris > 0 && !target_tris))
         return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->ins)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "dielectric occluders with filter_radon are not implemented on the GPU path");
     if (p->mesh)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'custom' vial with filter_radon is not implemented on the GPU path");
     if (p->dbl)

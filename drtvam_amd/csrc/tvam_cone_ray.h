@@ -115,11 +115,12 @@ __device__ __forceinline__ bool cn_segment(const TvamConsts& k, ConeRay& r) {
 // tp.seed, and its medium segment.  Returns whether it deposits.  The collimated projector takes
 // tvam_ray_world / tvam_segment_im (the ray records' own expressions), so that the export of such
 // a plan is the oracle's ray bit for bit.  RAY_ONLY: the world-space projector ray (r.o, r.d) alone,
-// for a caller that traces the vial itself (tvam_double.hip).
+// for a caller that traces the vial itself (tvam_double.hip).  rng: the ray's generator, left after
+// the prefix for a caller whose path loop goes on drawing (tvam_insert.hip).
 template <int MESH = CN_NO_MESH, bool RAY_ONLY = false>
 __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& tp, int al, int colc, int rowc,
-                                          uint64_t stream, ConeRay& r, const TvamMeshView* mesh = nullptr) {
-    TvamPcg rng;
+                                          uint64_t stream, ConeRay& r, TvamPcg& rng,
+                                          const TvamMeshView* mesh = nullptr) {
     const TvamPathDraws dr = tvam_path_draws<true, true>(k, tp, al, stream, rng);
     const float c = dr.c, sn = dr.sn;
     float xc, yc;
@@ -170,6 +171,14 @@ __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& 
     if (MESH == CN_GLASS) return cn_segment_glass(k, r);
     if (MESH != CN_NO_MESH) return cn_segment_mesh(k, *mesh, r);
     return cn_segment(k, r);
+}
+
+// ... for a caller that draws nothing after the prefix.
+template <int MESH = CN_NO_MESH, bool RAY_ONLY = false>
+__device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& tp, int al, int colc, int rowc,
+                                          uint64_t stream, ConeRay& r, const TvamMeshView* mesh = nullptr) {
+    TvamPcg rng;
+    return cn_ray_at<MESH, RAY_ONLY>(k, tp, al, colc, rowc, stream, r, rng, mesh);
 }
 
 // The projector ray alone.

@@ -320,6 +320,17 @@ void tvam_double_write_records(const TvamConsts& k, const TvamTiles& t, const fl
                                const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
 hipError_t tvam_launch_double_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
                                      float* segs, hipStream_t stream);
+// Dielectric occluders (tvam_insert.hip): every ray walked through the container, the black
+// occluders and the inserts' triangles (k.mesh: the hierarchy over all of them; tri_eta: device
+// [n_tris] eta by caller-order triangle), any number of medium segments per ray.  The per-ray
+// kernels and the export of the rays (16 floats per ray, may be null) and of the segments
+// ([max_segments][8] floats and a count per ray, may both be null).
+hipError_t tvam_launch_insert_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* tri_eta,
+                                   const float* pat, const int32_t* idxmap, const float* gin, float* out,
+                                   unsigned long long* counter, hipStream_t stream);
+hipError_t tvam_launch_insert_export(const TvamConsts& k, const TvamTiles& t, const float* tri_eta,
+                                     const int32_t* idxmap, float* rays, float* segs, int32_t max_segments,
+                                     int32_t* nseg, hipStream_t stream);
 // Extinction derivatives (tvam_dsigma.hip): one thread per (ray, sample) over the segment the plan's
 // forward marches (cone: a 3-D ray plan's cn_ray_at, else the collimated plans' planar first
 // segment).  FWD: the tangent film d dose / d sigma_t added into `tangent` (zeroed by the caller).

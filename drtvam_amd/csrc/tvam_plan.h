@@ -45,6 +45,8 @@ struct tvam_plan {
     TvamDevBuf<float> tgt, occ;   // target mesh (surface-aware films) and occluder triangles
     bool dbl = false;        // 'double_cylindrical' vial: four tubes traced per ray, two segments (tvam_double.h); implies cone
     bool traced = false;     // 'cylindrical' / 'square' vial traced per ray in 3-D (tvam_plan_create_traced, tvam_glass.h); implies cone
+    bool ins = false;        // dielectric occluders walked per ray (tvam_plan_create_inserts, tvam_insert.h); implies cone
+    TvamDevBuf<float> ins_eta;      // ... eta of each insert triangle, caller order (the hierarchy: mesh_*)
     TvamDevBuf<float4> mesh_nodes;  // 'custom' vial: the hierarchy over both meshes (TvamMesh)
     TvamDevBuf<float> mesh_tris;
     TvamDevBuf<int32_t> mesh_ids;

@@ -9,6 +9,7 @@
 //   * per-(xy-tile, angle) range of DMD columns whose rays can cross the tile.
 #include "tvam_plan.h"
 #include "tvam_glass.h"
+#include "tvam_insert.h"
 #include "tvam_mesh.h"
 
 #include <algorithm>
@@ -83,14 +84,36 @@ extern "C" void tvam_plan_destroy(tvam_plan* p) {
 
 // traced: the descriptor of tvam_plan_create_traced (a 'cylindrical' / 'square' vial on the 3-D
 // per-ray path, any projector kind)
-static int validate(const tvam_desc& d, bool traced = false) {
+// inserts: the descriptor of tvam_plan_create_inserts (dielectric occluders walked per ray)
+static int validate(const tvam_desc& d, bool traced = false, bool inserts = false) {
     if (d.abi_version != TVAM_ABI_VERSION) return tvam_fail(TVAM_ERR_INVALID, "tvam_desc.abi_version mismatch");
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED && d.projector_type != TVAM_PROJECTOR_TELECENTRIC &&
         d.projector_type != TVAM_PROJECTOR_LENS)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'collimated', 'telecentric' and 'lens' projectors are implemented on the GPU path");
     if (traced && d.vial_type != TVAM_VIAL_CYLINDRICAL && d.vial_type != TVAM_VIAL_SQUARE)
         return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_traced: vial_type must be TVAM_VIAL_CYLINDRICAL or TVAM_VIAL_SQUARE (other vials: tvam_plan_create and its siblings)");
-    if (d.vial_type == TVAM_VIAL_CUSTOM) {
+    if (inserts) {
+        // dielectric occluders (tvam_plan_create_inserts): every ray walks the container, the black
+        // occluders and the inserts in 3-D and runs the per-ray kernels of tvam_insert.hip, whose
+        // limits these are (Russian roulette is honoured: no limit on rr_depth)
+        auto no = [&](const char* what) {
+            return tvam_fail(TVAM_ERR_UNSUPPORTED,
+                             std::string("dielectric occluders with ") + what + " are not implemented on the GPU path");
+        };
+        if (d.vial_type == TVAM_VIAL_CUSTOM) return no("a 'custom' vial");
+        if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) return no("a 'double_cylindrical' vial");
+        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
+            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
+            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
+        }
+        if (!(d.vial_height > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "dielectric occluders need a positive vial height");
+        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
+        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
+        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
+        if (d.film_channels == 2) return no("a surface-aware film");
+        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
+        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the interfaces)");
+    } else if (d.vial_type == TVAM_VIAL_CUSTOM) {
         // mesh vial (tvam_plan_create_mesh): every ray is traced in 3-D through the interfaces and
         // runs the per-ray kernels of tvam_cone.hip, whose limits these are
         auto no = [&](const char* what) {
@@ -226,7 +249,8 @@ static int validate(const tvam_desc& d, bool traced = false) {
     }
     // the medium segment is path vertex 1 (index matched) or 2 (behind two glass
     // surfaces); Russian roulette starts at depth > rr_depth (volume.py:182-185)
-    if (d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL && d.rr_depth < (d.vial_type == TVAM_VIAL_INDEX_MATCHED ? 1 : 2))
+    if (!inserts && d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL &&
+        d.rr_depth < (d.vial_type == TVAM_VIAL_INDEX_MATCHED ? 1 : 2))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "Russian roulette before the medium segment (rr_depth too small) is not implemented");
     if (d.n_patterns <= 0 || d.res_x <= 0 || d.res_y <= 0) return tvam_fail(TVAM_ERR_INVALID, "projector resolution and n_patterns must be positive");
     if (d.crop_x <= 0 || d.crop_y <= 0 || d.crop_x > d.res_x || d.crop_y > d.res_y)
@@ -1065,6 +1089,19 @@ static void cyl_slot_lists(const tvam_desc& d, const TvamConsts& k, const std::v
     for (auto& v : len_of) std::vector<float>().swap(v);
 }
 
+// n_occ and the bounding box of the occluder triangles `tri` (TvamConsts::occ itself is the caller's).
+static void occ_bounds(TvamConsts& k, const float* tri, int32_t n) {
+    k.n_occ = n;
+    for (int a = 0; a < 3; ++a) {
+        k.occ_lo[a] = TVAM_INF;
+        k.occ_hi[a] = -TVAM_INF;
+    }
+    for (size_t i = 0; i < 9 * (size_t)n; ++i) {
+        k.occ_lo[i % 3] = std::min(k.occ_lo[i % 3], tri[i]);
+        k.occ_hi[i % 3] = std::max(k.occ_hi[i % 3], tri[i]);
+    }
+}
+
 // Plan creation, step by step.  Mesh upload: the target mesh (surface-aware films, TvamConsts::tgt)
 // and the occluder triangles with their bounding box (TvamConsts::occ).
 static int upload_meshes(tvam_plan* p) {
@@ -1078,15 +1115,7 @@ static int upload_meshes(tvam_plan* p) {
     if (d.n_occluder_tris > 0) {
         std::vector<float> tri(d.occluder_tris, d.occluder_tris + 9 * (size_t)d.n_occluder_tris);
         if ((rc = tvam_upload(p->occ, tri))) return rc;
-        p->k.n_occ = d.n_occluder_tris;
-        for (int a = 0; a < 3; ++a) {
-            p->k.occ_lo[a] = TVAM_INF;
-            p->k.occ_hi[a] = -TVAM_INF;
-        }
-        for (size_t i = 0; i < tri.size(); ++i) {
-            p->k.occ_lo[i % 3] = std::min(p->k.occ_lo[i % 3], tri[i]);
-            p->k.occ_hi[i % 3] = std::max(p->k.occ_hi[i % 3], tri[i]);
-        }
+        occ_bounds(p->k, tri.data(), d.n_occluder_tris);
     }
     p->bind();
     return 0;
@@ -1291,10 +1320,77 @@ static int upload_vial_meshes(tvam_plan* p, const float* outer, int32_t n_outer,
 }
 
 static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
-                       const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced = false);
+                       const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced = false,
+                       const tvam_insert* inserts = nullptr, int32_t n_inserts = 0);
 // tvam_double.hip
 int tvam_double_validate(const tvam_double_vial* v, float medium_ior);
 TvamDouble tvam_double_consts(const tvam_double_vial& v, float medium_ior);
+// tvam_insert.hip
+int tvam_inserts_validate(const TvamConsts& k, const tvam_insert* ins, int32_t n);
+void tvam_inserts_flatten(const tvam_insert* ins, int32_t n, std::vector<float>& tris, std::vector<float>& tri_eta);
+
+// Dielectric occluders: one hierarchy over every insert's triangles and each triangle's eta,
+// uploaded through the plan's owners.
+static int upload_inserts(tvam_plan* p, const tvam_insert* inserts, int32_t n_inserts) {
+    std::vector<float> tris, tri_eta;
+    tvam_inserts_flatten(inserts, n_inserts, tris, tri_eta);
+    int rc;
+    if ((rc = upload_vial_meshes(p, tris.data(), (int32_t)tri_eta.size(), nullptr, 0))) return rc;
+    return tvam_upload(p->ins_eta, tri_eta);
+}
+
+extern "C" int tvam_plan_create_inserts(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                        int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int rc = validate(*desc, false, true);
+    if (rc) return rc;
+    if ((rc = tvam_inserts_validate(make_consts(*desc, 0, 0), inserts, n_inserts))) return rc;
+    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out, false, inserts, n_inserts);
+}
+
+// The host walk of such a plan (tvam_insert.h), ray by ray: no device call.
+extern "C" int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                    const float* o, const float* d, int64_t n_rays, const float* u,
+                                    int32_t max_segments, float* segs, int32_t* nseg) {
+    if (!desc || n_rays < 0 || max_segments < 0 || (n_rays > 0 && (!o || !d || !nseg || (max_segments > 0 && !segs))))
+        return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    int rc = validate(*desc, false, true);
+    if (rc) return rc;
+    TvamConsts k = make_consts(*desc, 0, 0);
+    if ((rc = tvam_inserts_validate(k, inserts, n_inserts))) return rc;
+    if (desc->n_occluder_tris > 0) {
+        k.occ = desc->occluder_tris;
+        occ_bounds(k, desc->occluder_tris, desc->n_occluder_tris);
+    }
+    std::vector<float> tris, tri_eta;
+    tvam_inserts_flatten(inserts, n_inserts, tris, tri_eta);
+    TvamMeshHost h;
+    tvam_mesh_build(tris.data(), (int32_t)tri_eta.size(), h);
+    TvamInsertScene sc;
+    sc.mesh.nodes = h.nodes.data(), sc.mesh.tris = h.tris.data(), sc.mesh.ids = h.ids.data();
+    sc.mesh.n_nodes = (int32_t)(h.nodes.size() / 2), sc.mesh.n_tris = (int32_t)tri_eta.size(), sc.mesh.n_inner = 0;
+    sc.tri_eta = tri_eta.data();
+    for (int64_t i = 0; i < n_rays; ++i) {
+        TvamInsertWalk w;
+        tvam_insert_start(w, o + 3 * i, d + 3 * i);
+        TvamInsertHostDraws dr{u ? u + 4 * (size_t)k.max_depth * (size_t)i : nullptr};
+        float* row = segs + 8 * (size_t)max_segments * (size_t)i;
+        if (max_segments > 0) std::fill(row, row + 8 * (size_t)max_segments, 0.0f);
+        int32_t s = 0;
+        float o2[3], d2[3], maxt, att;
+        while (tvam_insert_next(k, sc, u != nullptr, dr, w, o2, d2, maxt, att)) {
+            if (s < max_segments) {
+                float* sg = row + 8 * s;
+                sg[0] = o2[0], sg[1] = o2[1], sg[2] = o2[2], sg[3] = maxt;
+                sg[4] = d2[0], sg[5] = d2[1], sg[6] = d2[2], sg[7] = att;
+            }
+            ++s;
+        }
+        nseg[i] = s;
+    }
+    return 0;
+}
 
 extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** out) {
     if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
@@ -1359,13 +1455,14 @@ extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_t
 }
 
 static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_outer, const float* inner,
-                       int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced) {
+                       int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced,
+                       const tvam_insert* inserts, int32_t n_inserts) {
     tvam_desc d = d_in;
     if (dbl) {  // the host tables (tiles, slots) are sized by the medium's tube and the outermost one
         d.vial_r = dbl->r_int_outer;
         d.vial_r_ext = dbl->r_ext_outer;
     }
-    int rc = validate(d, traced);
+    int rc = validate(d, traced, inserts != nullptr);
     if (rc) return rc;
     int a0 = d.angle_begin, a1 = d.angle_end < 0 ? d.n_patterns : d.angle_end;
     if (a0 < 0 || a1 > d.n_patterns || a0 > a1) return tvam_fail(TVAM_ERR_INVALID, "invalid angle shard");
@@ -1392,12 +1489,18 @@ static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_oute
         p->empty = d.max_depth < 3;  // the first deposit is at loop iteration 2
         p->k.dbl = tvam_double_consts(*dbl, d.medium_ior);
     }
+    p->ins = inserts != nullptr;
+    if (p->ins) {  // a glass vial under the inserts is a traced one (the planar tables are not this path's)
+        traced = p->cyl;
+        p->empty = d.max_depth < (p->cyl ? 3 : 2);
+    }
     p->traced = traced;
     if (traced) p->cyl = false;  // (the planar tables and ray records of a refracting vial are not this path's)
-    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh || p->dbl || traced;
+    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh || p->dbl || traced || p->ins;
     p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
     if ((rc = upload_meshes(p.get())) || (rc = tile_geometry(p.get()))) return rc;
     if (p->mesh && (rc = upload_vial_meshes(p.get(), outer, n_outer, inner, n_inner))) return rc;
+    if (p->ins && (rc = upload_inserts(p.get(), inserts, n_inserts))) return rc;
 
     std::vector<float2> cs;
     std::vector<float4> ang;
@@ -1465,7 +1568,8 @@ extern "C" int tvam_plan_kernel_time(tvam_plan* p, int32_t enable, double* total
         // the plan's dominant forward kernel: the brick march of a scattering medium, else the
         // voxel-driven planar forward where it serves, else the per-ray tile forward
         // (telecentric / lens: the brick march of the binned forward, else the per-ray atomic forward)
-        g_kt.kind = p->cone ? (tvam_cone_binned(p) ? TVAM_KT_BRICK : TVAM_KT_CONE)
+        // (dielectric occluders: the per-ray atomic forward alone)
+        g_kt.kind = p->cone ? (tvam_cone_binned(p) && !p->ins ? TVAM_KT_BRICK : TVAM_KT_CONE)
                             : (p->desc.albedo != 0.0f ? TVAM_KT_BRICK : (p->planar_fwd ? TVAM_KT_PLANAR : TVAM_KT_TILE));
         g_kt.on = true;
     }

@@ -50,7 +50,11 @@ class Projection:
             self.device = torch.device("cuda", torch.cuda.current_device())
         plan = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            if self.desc.vial_type == _abi.VIAL_CUSTOM:  # the meshes travel beside the struct (set_vial_meshes)
+            if self.desc.inserts:  # dielectric occluders travel beside the struct (set_inserts)
+                ins = self.desc.inserts
+                _abi.check(self.lib.tvam_plan_create_inserts(ctypes.byref(self.desc), _abi.insert_array(ins), len(ins),
+                                                             self.device.index, ctypes.byref(plan)))
+            elif self.desc.vial_type == _abi.VIAL_CUSTOM:  # the meshes travel beside the struct (set_vial_meshes)
                 outer = getattr(self.desc, "_vial_outer", None)
                 inner = getattr(self.desc, "_vial_inner", None)
                 _abi.check(self.lib.tvam_plan_create_mesh(
@@ -309,6 +313,29 @@ class Projection:
                 self._plan, None if active_pixels is None else active_pixels.data_ptr(), int(n_active), int(spp),
                 seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
         return out
+
+    def insert_segments(self, n_active: Optional[int] = None, active_pixels: Optional[torch.Tensor] = None,
+                        spp: int = 1, seed: int = 0, max_segments: int = 8):
+        """Every medium segment of a call's rays through a resin with dielectric occluders
+        (tvam_plan_insert_segments): (segs [n_active * spp, max_segments, 8] float32 in sampler-stream order:
+        o2[0:3], maxt [3], d2[4:7], weight [7] (the whole per-ray weight times the attenuation the segment
+        starts with), zeros past a ray's segments; nseg [n_active * spp] int32, the segments each ray has)."""
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+            n_active = int(active_pixels.numel())
+        elif n_active is None:
+            a0, a1 = self.desc.angle_begin, (self.desc.angle_end if self.desc.angle_end >= 0 else self.desc.n_patterns)
+            n_active = (a1 - a0) * self.desc.crop_y * self.desc.crop_x
+        if self.desc.regular_sampling:
+            spp = 1  # common.py:49-51
+        rows = int(n_active) * int(spp)
+        segs = torch.zeros((rows, int(max_segments), 8), dtype=torch.float32, device=self.device)
+        nseg = torch.zeros((rows,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_plan_insert_segments(
+                self._plan, None if active_pixels is None else active_pixels.data_ptr(), int(n_active), int(spp),
+                seed & 0xFFFFFFFF, int(max_segments), segs.data_ptr(), nseg.data_ptr(), _stream_ptr(self.device)))
+        return segs, nseg
 
     @property
     def cone(self) -> bool:

@@ -58,15 +58,41 @@ class Container:
         if self.occlusions:
             import numpy as np
             from .utils import read_ply
-            tris = []
+            tris, inserts = [], []
             for occ in self.occlusions:
                 bsdf = occ.get("bsdf")
-                if bsdf is not None and not (bsdf.get("type") == "diffuse" and
-                                             float(bsdf.get("reflectance", {}).get("value", 0.0)) == 0.0):
-                    raise NotImplementedError("occluders must be black diffuse (the reference default)")
+                kind = None if bsdf is None else bsdf.get("type")
+                black = bsdf is None or (kind == "diffuse" and
+                                         float(bsdf.get("reflectance", {}).get("value", 0.0)) == 0.0)
+                if not black and kind != "dielectric":
+                    raise NotImplementedError(f"occluder BSDF '{kind}' ({occ.get('filename')}): occluders must be black "
+                                              "diffuse (the reference default) or dielectric")
+                if kind == "dielectric" and not occ.get("face_normals", True):
+                    raise NotImplementedError(f"dielectric occluder {occ.get('filename')}: face_normals: false "
+                                              "(interpolated shading normals) is not implemented on the GPU path")
                 v, f = read_ply(occ["filename"])
-                tris.append(np.asarray(v, np.float32)[np.asarray(f)])
-            desc.set_occluders(np.concatenate(tris))
+                t = np.asarray(v, np.float32)[np.asarray(f)]
+                if kind == "dielectric":  # Mitsuba's defaults: int_ior 'bk7', ext_ior 'air'; the BSDF's own numbers
+                    inserts.append((t, lookup_ior(bsdf.get("int_ior", "bk7")), lookup_ior(bsdf.get("ext_ior", "air"))))
+                else:
+                    tris.append(t)
+            if tris:
+                desc.set_occluders(np.concatenate(tris))
+            if inserts:  # beside the descriptor, as set_vial_meshes: engine.Projection -> tvam_plan_create_inserts
+                desc.set_inserts(inserts)
+
+    def add_occlusions(self, dd):
+        """The occlusions as scene shapes (geometry.py:55-72): black diffuse unless the entry has a 'bsdf'."""
+        default_bsdf = {"type": "diffuse", "reflectance": {"type": "spectrum", "value": 0.0}}
+        for occ in self.occlusions:
+            dd["occlusion" + occ["filename"].replace("/", "_").replace(".", "_")] = {
+                'type': 'ply',
+                'face_normals': occ.get("face_normals", True),
+                'filename': occ["filename"],
+                'bsdf': occ.get("bsdf", default_bsdf),
+                'exterior': {'type': 'ref', 'id': 'printing_medium'},
+            }
+        return dd
 
 
 # Named refractive indices (Mitsuba's ior table, restated for the names a config may use)
@@ -96,7 +122,7 @@ class IndexMatchedVial(Container):
         self.height = params.get('height', 40.)
 
     def to_dict(self):
-        return {
+        return self.add_occlusions({
             'printing_medium': self.medium_dict(),
             'vial_exterior': {
                 'type': 'cylinder',
@@ -106,7 +132,7 @@ class IndexMatchedVial(Container):
                 'bsdf': {'type': 'null'},
                 'interior': {'type': 'ref', 'id': 'printing_medium'},
             },
-        }
+        })
 
     def fill_desc(self, desc):
         self._fill_medium(desc)
@@ -126,7 +152,7 @@ class CylindricalVial(Container):
         self.vial_ior = params['ior']
 
     def to_dict(self):
-        return {
+        return self.add_occlusions({
             'printing_medium': self.medium_dict(),
             'vial_exterior': {'type': 'cylinder', 'p0': [0., 0., -0.5 * self.height], 'p1': [0., 0., 0.5 * self.height],
                               'radius': self.r_ext,
@@ -135,7 +161,7 @@ class CylindricalVial(Container):
                               'radius': self.r_int,
                               'bsdf': {'type': 'dielectric', 'ext_ior': self.vial_ior, 'int_ior': self.medium_ior},
                               'interior': {'type': 'ref', 'id': 'printing_medium'}},
-        }
+        })
 
     def fill_desc(self, desc):
         self._fill_medium(desc)
@@ -165,12 +191,13 @@ class SquareVial(Container):
         desc.vial_ior = lookup_ior(self.vial_ior)
 
     def to_dict(self):
-        return {'printing_medium': self.medium_dict(),
+        return self.add_occlusions({
+                'printing_medium': self.medium_dict(),
                 'vial_exterior': {'type': 'cube', 'scale': (0.5 * self.w_ext, 0.5 * self.w_ext, 0.5 * self.height),
                                   'bsdf': {'type': 'dielectric', 'int_ior': self.vial_ior}},
                 'vial_interior': {'type': 'cube', 'scale': (0.5 * self.w_int, 0.5 * self.w_int, 0.45 * self.height),
                                   'bsdf': {'type': 'dielectric', 'ext_ior': self.vial_ior, 'int_ior': self.medium_ior},
-                                  'interior': {'type': 'ref', 'id': 'printing_medium'}}}
+                                  'interior': {'type': 'ref', 'id': 'printing_medium'}}})
 
 
 class CustomVial(Container):
@@ -185,12 +212,13 @@ class CustomVial(Container):
         self.filename_vial_inner = params["filename_vial_inner"]
 
     def to_dict(self):
-        return {'printing_medium': self.medium_dict(),
+        return self.add_occlusions({
+                'printing_medium': self.medium_dict(),
                 'vial_exterior': {'type': 'ply', 'face_normals': True, 'filename': self.filename_vial_outer,
                                   'bsdf': {'type': 'dielectric', 'int_ior': self.vial_ior, 'ext_ior': 'air'}},
                 'vial_interior': {'type': 'ply', 'filename': self.filename_vial_inner, 'face_normals': True,
                                   'bsdf': {'type': 'dielectric', 'ext_ior': self.vial_ior, 'int_ior': self.medium_ior},
-                                  'interior': {'type': 'ref', 'id': 'printing_medium'}}}
+                                  'interior': {'type': 'ref', 'id': 'printing_medium'}}})
 
     def fill_desc(self, desc):
         """Both PLYs as world-space triangles (face normals from the winding: both surfaces must be
@@ -229,7 +257,7 @@ class DoubleCylindricalVial(Container):
 
     def to_dict(self):
         ref = {'type': 'ref', 'id': 'printing_medium'}
-        return {
+        return self.add_occlusions({
             'printing_medium': self.medium_dict(),
             'outer_vial': self._tube(self.r_ext_outer, {'int_ior': self.vial_ior_outer}),
             'outer_vial_interior': self._tube(self.r_int_outer,
@@ -238,7 +266,7 @@ class DoubleCylindricalVial(Container):
                                      exterior=ref),
             'inner_vial_interior': self._tube(self.r_int_inner,
                                               {'ext_ior': self.vial_ior_inner, 'int_ior': self.inside_inner_ior}),
-        }
+        })
 
     def fill_desc(self, desc):
         """The medium, the height and vial_type in the descriptor; the radii and the glass / core IORs

@@ -72,14 +72,20 @@ class TVAMIntegrator:
         from ..engine import Projection
         d = self.desc(scene, sensor)
         dev = torch.device(device) if device is not None else scene.projector.device
-        key = (bytes(memoryview(ctypes.string_at(ctypes.addressof(d), ctypes.sizeof(d)))), d.traced_vial, str(dev))
+        # (what travels beside the struct: the traced mark, the dielectric occluders' triangles and IORs and a
+        # 'custom' vial's meshes, by the digest of their bytes: a moved piece is another plan)
+        import hashlib
+        digest = lambda t: None if t is None else hashlib.sha1(t.tobytes()).hexdigest()
+        beside = (d.traced_vial, tuple((digest(t), ni, ne) for t, ni, ne in d.inserts),
+                  digest(getattr(d, "_vial_outer", None)), digest(getattr(d, "_vial_inner", None)))
+        key = (bytes(memoryview(ctypes.string_at(ctypes.addressof(d), ctypes.sizeof(d)))), beside, str(dev))
         proj = self._plans.get(key)
         if proj is None:
             # a fit of the extinction builds a plan per step: plans whose descriptors differ in
             # sigma_t alone evict one another
             fam = d.copy()
             fam.sigma_t = 0.0
-            fam = (bytes(memoryview(ctypes.string_at(ctypes.addressof(fam), ctypes.sizeof(fam)))), d.traced_vial, str(dev))
+            fam = (bytes(memoryview(ctypes.string_at(ctypes.addressof(fam), ctypes.sizeof(fam)))), beside, str(dev))
             old = self._families.pop(fam, None)
             if old is not None:
                 self._plans.pop(old).close()

@@ -537,8 +537,9 @@ class TvamProblem(ShardedLoop):
         custom = int(full_desc.vial_type) == 3  # _abi.VIAL_CUSTOM: mesh interfaces, 3-D per-ray path
         double = int(full_desc.vial_type) == 4  # _abi.VIAL_DOUBLE_CYLINDRICAL: nested tubes, 3-D per-ray path
         traced = full_desc.traced_vial  # glass tube / cuvette traced per ray (tvam_plan_create_traced): 3-D per-ray path
+        inserts = bool(full_desc.inserts)  # dielectric occluders walked per ray (tvam_plan_create_inserts): 3-D per-ray path
         if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0 or custom or double
-                                      or traced):
+                                      or traced or inserts):
             # every path marched, as the reference marches every active pixel (projector.py:66-70,
             # common.py:81-82): a scattering scene's paths (and a telecentric / lens projector's
             # binned first segments) then do not depend on the pattern, and
@@ -569,7 +570,12 @@ class TvamProblem(ShardedLoop):
             raise NotImplementedError("filter_radon with a 'double_cylindrical' vial is not implemented on the GPU path")
         if double and 'filter_corner' in config and filter_pixels:
             raise NotImplementedError("filter_corner with a 'double_cylindrical' vial is not implemented on the GPU path")
-        cone = int(full_desc.projector_type) != 0 or custom or double or traced
+        if inserts and shard == 'slab':
+            raise ValueError("z-slab sharding needs planar rays: dielectric occluders refract rays at tilted faces "
+                             "and take them out of their slice (use shard 'angle')")
+        if inserts and config.get('filter_radon', False) and filter_pixels:
+            raise NotImplementedError("filter_radon with dielectric occluders is not implemented on the GPU path")
+        cone = int(full_desc.projector_type) != 0 or custom or double or traced or inserts
         if cone and shard == 'slab':
             raise ValueError("z-slab sharding needs planar rays: the 'telecentric' and 'lens' projectors' rays "
                              "leave their slice (use shard 'angle')")

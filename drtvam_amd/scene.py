@@ -56,6 +56,14 @@ def _medium_from(d, ior):
 def _container_from_shapes(scene_dict):
     media = {k: v for k, v in scene_dict.items() if isinstance(v, dict) and v.get('type') == 'homogeneous'}
     shapes = {k: v for k, v in scene_dict.items() if isinstance(v, dict) and v.get('type') in ('cylinder', 'cube', 'ply')}
+    # Container.add_occlusions: 'ply' shapes whose exterior is the medium; their 'bsdf' (black diffuse or
+    # dielectric) and 'face_normals' go back into the container's 'occlusions'
+    occl = {k: v for k, v in shapes.items() if k.startswith('occlusion') and v['type'] == 'ply' and 'exterior' in v
+            and 'interior' not in v}
+    shapes = {k: v for k, v in shapes.items() if k not in occl}
+    occlusions = [{'filename': v['filename'], 'face_normals': v.get('face_normals', True),
+                   **({'bsdf': v['bsdf']} if 'bsdf' in v else {})} for v in occl.values()]
+    extra = {'occlusions': occlusions} if occlusions else {}
     holder = [(k, v) for k, v in shapes.items() if 'interior' in v]
     if not holder:
         return None
@@ -71,7 +79,7 @@ def _container_from_shapes(scene_dict):
         if abs(p0[0]) + abs(p0[1]) + abs(p1[0]) + abs(p1[1]) > 0 or abs(p0[2] + p1[2]) > 1e-9:
             raise NotImplementedError("only vials centred on the z axis are supported")
         return IndexMatchedVial({'r': shp['radius'], 'height': float(abs(p1[2] - p0[2])),
-                                 'medium': _medium_from(interior, 1.0)})
+                                 'medium': _medium_from(interior, 1.0), **extra})
     if shp['type'] == 'cylinder' and bsdf.get('type') == 'dielectric':
         outer = [v for k, v in shapes.items() if k != name and v['type'] == 'cylinder']
         if len(outer) == 1:
@@ -79,7 +87,7 @@ def _container_from_shapes(scene_dict):
             return CylindricalVial({'r_int': shp['radius'], 'r_ext': outer[0]['radius'],
                                     'height': float(abs(p1[2] - p0[2])),
                                     'ior': bsdf.get('ext_ior', 1.5),
-                                    'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
+                                    'medium': _medium_from(interior, bsdf.get('int_ior', 1.0)), **extra})
         if len(outer) == 3:  # DoubleCylindricalVial.to_dict: four nested dielectric tubes
             by_r = sorted(outer + [shp], key=lambda v: -v['radius'])
             if by_r[1] is shp and 'exterior' in by_r[2] and all(v.get('bsdf', {}).get('type') == 'dielectric' for v in by_r):
@@ -90,14 +98,14 @@ def _container_from_shapes(scene_dict):
                     'height': float(abs(p1[2] - p0[2])), 'ior_outer': bsdf.get('ext_ior', 1.5),
                     'ior_inner': by_r[2]['bsdf'].get('int_ior', 1.5),
                     'ior_inside_inner': by_r[3]['bsdf'].get('int_ior', 1.0),
-                    'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
+                    'medium': _medium_from(interior, bsdf.get('int_ior', 1.0)), **extra})
     if shp['type'] == 'ply' and bsdf.get('type') == 'dielectric':  # CustomVial.to_dict: two dielectric meshes
         outer = [v for k, v in shapes.items() if k != name and v['type'] == 'ply'
                  and v.get('bsdf', {}).get('type') == 'dielectric']
         if len(outer) == 1:
             return CustomVial({'filename_vial_outer': outer[0]['filename'], 'filename_vial_inner': shp['filename'],
                                'ior': bsdf.get('ext_ior', outer[0]['bsdf'].get('int_ior', 1.5)),
-                               'medium': _medium_from(interior, bsdf.get('int_ior', 1.0))})
+                               'medium': _medium_from(interior, bsdf.get('int_ior', 1.0)), **extra})
     raise NotImplementedError(f"container shape '{name}' is not supported by the GPU engine")
 
 

@@ -302,6 +302,70 @@ int tvam_plan_create_traced(const tvam_desc* desc, int device, tvam_plan** plan)
 int tvam_traced_segments(const tvam_desc* desc, const float* o, const float* d, int64_t n_rays, float* segs);
 
 /*
+ * A dielectric occluder (geometry.py:55-72 with a 'bsdf' entry of type 'dielectric'): a transparent
+ * insert inside the resin, the overprinting case.  tris: host [n_tris][3][3], a closed mesh wound
+ * outwards (face normal normalize((v1 - v0) x (v2 - v0))); int_ior / ext_ior: the BSDF's own numbers
+ * (eta = int_ior / ext_ior whatever the resin's IOR is).  The insert's exterior is the printing
+ * medium and it has no interior medium: a ray refracts into it, crosses it without dose or
+ * attenuation, refracts out and goes on depositing.
+ */
+typedef struct tvam_insert {
+    const float* tris;
+    int32_t n_tris;
+    float int_ior;
+    float ext_ior;
+} tvam_insert;
+
+/*
+ * A plan whose resin holds dielectric occluders, behind an 'index_matched', 'cylindrical' or
+ * 'square' vial (the last two as tvam_plan_create_traced describes them) with any of the three
+ * projectors.  Every ray runs the path loop of volume.py:179-272 in transmission-only mode: per
+ * iteration one Russian roulette draw (it acts when depth > rr_depth, q = min(0.99, attenuation)),
+ * the nearest hit over the container's surfaces, then the descriptor's black occluders, then the
+ * insert triangles (a later candidate wins only when strictly nearer; none: the path ends and a
+ * segment in progress deposits nothing), a medium segment up to the hit when the ray is in the
+ * resin, then: a black occluder ends the path; any other surface multiplies the attenuation by its
+ * Fresnel transmission (0, total internal reflection, ends the path) and, after a medium segment,
+ * by e^{-sigma_t t}; the medium flag is on behind the container's medium boundary crossed inwards
+ * and behind an insert face crossed outwards, off otherwise.  At most max_depth surfaces.  A ray so
+ * deposits along any number of segments, which may leave their z-plane: the plan runs per-ray 3-D
+ * kernels (forward: float atomics; adjoint: a gather).  The triangles are read here and not kept.
+ * TVAM_ERR_INVALID, naming the insert and the triangle or vertex: null or empty meshes, non-finite
+ * vertices, zero-area triangles, non-positive IORs, a vertex outside the resin (tubes: radius >=
+ * vial_r or |z| > vial_height / 2; square: outside the inner cuboid).  TVAM_ERR_UNSUPPORTED, as
+ * "dielectric occluders with <what>": albedo > 0, the ratio / delta sensors, a surface-aware film,
+ * film slabs, transmission_only = 0, a 'custom' or 'double_cylindrical' vial.  All of it is checked
+ * before any device call.  On such a plan tvam_plan_rays gives the projector ray and the first
+ * segment in the traced plans' layout, tvam_corner and tvam_count_visits serve it, and tvam_radon,
+ * tvam_forward_dsigma, tvam_adjoint_dsigma, tvam_forward_slices, tvam_adjoint_slices and
+ * tvam_plan_segments refuse it by name.
+ */
+int tvam_plan_create_inserts(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts, int device,
+                             tvam_plan** plan);
+
+/*
+ * The medium segments of that walk on the host, with the code the kernels run and no GPU touched:
+ * n_rays world rays (o, d: [n_rays][3], host); u: [n_rays][max_depth][4] host, the four draws of
+ * each loop iteration (roulette, then the BSDF's three, ignored), or NULL: roulette never acts.
+ * segs: host [n_rays][max_segments][8], each segment o2[3], maxt, d2[3], weight = the attenuation
+ * the segment starts with, zeros past the ray's segments; nseg: host [n_rays], the segments the ray
+ * has (beyond max_segments they are counted and not written).  TVAM_ERR_INVALID /
+ * TVAM_ERR_UNSUPPORTED as tvam_plan_create_inserts.
+ */
+int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts, const float* o,
+                         const float* d, int64_t n_rays, const float* u, int32_t max_segments, float* segs,
+                         int32_t* nseg);
+
+/*
+ * The same on the device for a call's rays: segs [n_active * spp][max_segments][8] floats (16-byte
+ * aligned) and nseg [n_active * spp] in sampler-stream order as tvam_plan_segments defines it, the
+ * weight as there (the whole per-ray weight times the attenuation the segment starts with).
+ * TVAM_ERR_UNSUPPORTED on a plan that tvam_plan_create_inserts did not make.
+ */
+int tvam_plan_insert_segments(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
+                              uint32_t seed, int32_t max_segments, float* segs, int32_t* nseg, void* hip_stream);
+
+/*
  * Forward projection (primal render).  Writes the whole film
  * dose[z][y][x][C] (film order) = inv_vol * sum over rays of this plan's
  * angle shard; every voxel is overwritten (no pre-zeroing needed).
