@@ -209,23 +209,29 @@ static int bind_active(tvam_plan* p, const TvamConsts& k, const float* active_da
     return 0;
 }
 
+// A 3-D ray plan's per-ray kernels (tvam_ray3d.hip) over the plan's walk.
+static hipError_t launch_ray3d(int mode, const tvam_plan* p, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                               const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
+                               hipStream_t stream) {
+    return tvam_launch_ray3d(mode, tvam_plan_walk(p), k, t, p->ins_eta.get(), pat, idxmap, gin, out, counter, stream);
+}
+
 // Segments of a call that cross slices -- the scattered segments after each path's first medium
-// segment (writer = nullptr), or the 3-D first segments of a telecentric / lens forward (their record
-// writer): through the brick bins when `binned`, else (or on a grid beyond the packed records' range)
-// the per-ray atomics / gathers of `per_ray`.
-typedef hipError_t (*TvamPerRay)(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
-                                 const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
-                                 hipStream_t stream);
+// segment (walk = TVAM_WALK_NONE), or the 3-D segments of a 3-D ray plan's forward (its walk): through
+// the brick bins when `binned`, else (or on a grid beyond the packed records' range) the per-ray
+// atomics / gathers.
 static int scattered_segments(int mode, tvam_plan* p, const TvamConsts& k, const TvamTiles& t, const float* pat,
                               const int32_t* idxmap, const float* gin, float* out, hipStream_t stream, bool binned,
-                              TvamRecWriter writer, TvamPerRay per_ray, const char* what, int writer_slots = 1) {
+                              int walk, const char* what) {
     hipError_t e = hipErrorNotSupported;
     if (mode == TVAM_MODE_FWD) p->bins.acc_float = tvam_knob("TVAM_BIN_FLOAT", 0);
     if (binned)
-        e = tvam_scatter_binned(mode, k, t, pat, idxmap, gin, out, p->bins, stream, writer, writer_slots);
+        e = tvam_scatter_binned(mode, k, t, pat, idxmap, gin, out, p->bins, stream, walk);
     else
         for (auto& v : p->bins.st) v = 0;  // nothing binned
-    if (e == hipErrorNotSupported) e = per_ray(mode, k, t, pat, idxmap, gin, out, nullptr, stream);
+    if (e == hipErrorNotSupported)
+        e = walk == TVAM_WALK_NONE ? tvam_launch_scatter_paths(mode, k, t, pat, idxmap, gin, out, nullptr, stream)
+                                   : launch_ray3d(mode, p, k, t, pat, idxmap, gin, out, nullptr, stream);
     if (e == hipErrorIllegalState) return bin_mismatch_fail(p);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, what);
 }
@@ -284,17 +290,14 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
     if ((rc = bind_active(p, kc, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
     if (p->general) {
         TvamTiles t = call_tiles(p, spp, seed);
-        if (p->ins) {  // any number of medium segments per ray: the per-ray atomics alone
-            e = tvam_launch_insert_rays(TVAM_MODE_FWD, kc, t, p->ins_eta.get(), pat, idxmap, nullptr, dose, nullptr, stream);
-            return e == hipSuccess ? 0 : tvam_hip_fail(e, "dielectric-occluder forward launch");
+        if (p->cone) {  // a record slot per possible segment; any number of them: the per-ray atomics alone
+            const int walk = tvam_plan_walk(p);
+            return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream,
+                                      tvam_walk_slots(walk) > 0 && tvam_cone_binned(p), walk,
+                                      p->ins   ? "dielectric-occluder forward launch"
+                                      : p->dbl ? "double-vial forward launch"
+                                               : "projector-ray forward launch");
         }
-        if (p->dbl)  // two medium segments per ray: two record slots per path
-            return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream, tvam_cone_binned(p),
-                                      tvam_double_write_records, tvam_launch_double_rays,
-                                      "double-vial forward launch", 2);
-        if (p->cone)
-            return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream, tvam_cone_binned(p),
-                                      tvam_cone_write_records, tvam_launch_cone_rays, "projector-ray forward launch");
         e = tvam_launch_general_paths(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, nullptr, stream);
         return e == hipSuccess ? 0 : tvam_hip_fail(e, "path forward launch");
     }
@@ -334,8 +337,7 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
     }
     if (p->desc.albedo != 0.0f) {  // scattered segments (after each path's first medium segment)
         return scattered_segments(TVAM_MODE_FWD, p, kc, call_tiles(p, spp, seed), pat, idxmap, nullptr, dose, stream,
-                                  !(p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC), nullptr, tvam_launch_scatter_paths,
-                                  "scatter forward launch");
+                                  !(p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC), TVAM_WALK_NONE, "scatter forward launch");
     }
     return 0;
 }
@@ -424,10 +426,8 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     if (p->general) {
         if (p->empty) return 0;
         TvamTiles t = call_tiles(p, spp, seed);
-        e = p->ins    ? tvam_launch_insert_rays(TVAM_MODE_ADJ, k, t, p->ins_eta.get(), nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
-            : p->dbl  ? tvam_launch_double_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
-            : p->cone ? tvam_launch_cone_rays(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
-                      : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
+        e = p->cone ? launch_ray3d(TVAM_MODE_ADJ, p, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+                    : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
         return e == hipSuccess ? 0 : tvam_hip_fail(e, "path adjoint launch");
     }
     if (p->surface) {
@@ -452,8 +452,8 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     }
     if (p->desc.albedo != 0.0f && !p->empty) {
         return scattered_segments(TVAM_MODE_ADJ, p, k, call_tiles(p, spp, seed), nullptr, idxmap, grad_dose, grad_active,
-                                  stream, !(p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC), nullptr,
-                                  tvam_launch_scatter_paths, "scatter adjoint launch");
+                                  stream, !(p->desc.flags & TVAM_FLAG_SCATTER_ATOMIC), TVAM_WALK_NONE,
+                                  "scatter adjoint launch");
     }
     return 0;
 }
@@ -520,8 +520,9 @@ extern "C" int tvam_adjoint_dsigma(tvam_plan* p, const float* active_data, const
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "extinction gradient launch");
 }
 
-// The rays of a call (tvam_cone.hip's ray generation serves every projector kind); `segs`: both
-// medium segments of a 'double_cylindrical' plan instead (tvam_plan_segments).
+// The rays of a call (tvam_ray3d.hip's export serves every projector kind); `segs`: the medium
+// segments of a 'double_cylindrical' plan (tvam_plan_segments, two per ray) or of a plan with
+// dielectric occluders (tvam_plan_insert_segments, max_segments per ray and their count) instead.
 static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
                        float* rays, float* segs, void* stream_, int32_t max_segments = 0, int32_t* nseg = nullptr);
 
@@ -542,7 +543,7 @@ extern "C" int tvam_plan_segments(tvam_plan* p, const uint32_t* active_pixels, u
     if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with dielectric occluders has any number of segments per ray (tvam_plan_insert_segments)");
     if (!p->dbl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: 'double_cylindrical' vial plans only");
     if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_segments: segs must be 16-byte aligned");
-    return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_);
+    return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_, 2);
 }
 
 extern "C" int tvam_plan_insert_segments(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
@@ -566,9 +567,7 @@ static int export_rays(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_a
     const int32_t* idxmap = nullptr;
     if ((rc = bind_active(p, k, nullptr, active_pixels, n_active, stream, nullptr, &idxmap))) return rc;
     TvamTiles t = call_tiles(p, spp, seed);
-    e = p->ins   ? tvam_launch_insert_export(k, t, p->ins_eta.get(), idxmap, rays, segs, max_segments, nseg, stream)
-        : p->dbl ? tvam_launch_double_export(k, t, idxmap, rays, segs, stream)
-                 : tvam_launch_cone_export(k, t, idxmap, rays, stream);
+    e = tvam_launch_ray3d_export(tvam_plan_walk(p), k, t, p->ins_eta.get(), idxmap, rays, segs, max_segments, nseg, stream);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "ray export launch");
 }
 
@@ -583,10 +582,8 @@ extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint
     if (e != hipSuccess) return tvam_hip_fail(e, "hipMemset");
     TvamTiles t = call_tiles(p, spp, seed);
     if (p->general) {
-        e = p->ins    ? tvam_launch_insert_rays(TVAM_MODE_COUNT, k, t, p->ins_eta.get(), nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
-            : p->dbl  ? tvam_launch_double_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
-            : p->cone ? tvam_launch_cone_rays(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
-                      : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
+        e = p->cone ? launch_ray3d(TVAM_MODE_COUNT, p, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
+                    : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
     } else if (p->surface) {
         e = tvam_launch_surface_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, nullptr, p->counter.get(),
                                       nullptr);

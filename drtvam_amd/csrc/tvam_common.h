@@ -99,7 +99,7 @@ struct TvamConsts {
     // fixed-point forward bound: |voxel sum| <= max|em| * vox_chord * rays_per_voxel * rows * spp
     float vox_chord;      // min(1, sigma_t * sqrt(2) * max(hx, hy)): bound of 1 - exp(-st dt) in a voxel
     float rays_per_voxel; // n_shard * (ceil(sqrt(2) * max(hx, hy) / pixel_size_x) + 1)
-    // telecentric / lens projectors (projector.py:199-296; tvam_cone.hip)
+    // telecentric / lens projectors (projector.py:199-296; tvam_ray3d.hip)
     int32_t proj_type;    // TVAM_PROJECTOR_*
     float ap_r;           // 'aperture_radius'
     float focus;          // 'focus_distance'

@@ -1,9 +1,9 @@
 // tvam_cone_ray.h -- ray generation of the telecentric / lens projectors (projector.py:199-296),
-// shared by tvam_cone.hip (forward, adjoint, export) and tvam_corner.hip (the 'filter_corner'
+// shared by tvam_ray3d.hip (forward, adjoint, export) and tvam_corner.hip (the 'filter_corner'
 // first-hit pass): the sampler draws, get_ray, CircularMotion's to_world and the medium segment
 // behind the index-matched vial, behind the mesh interfaces of a 'custom' vial or behind the two
 // analytic glass surfaces of a traced 'cylindrical' / 'square' vial (tvam_glass.h), and the per-ray
-// DDA of a 3-D segment (cn_dda), which tvam_cone.hip and tvam_double.hip march (device only).
+// DDA of a 3-D segment (cn_dda), which tvam_ray3d.hip marches (device only).
 #pragma once
 #include "tvam_glass.h"
 #include "tvam_mesh.h"
@@ -115,8 +115,8 @@ __device__ __forceinline__ bool cn_segment(const TvamConsts& k, ConeRay& r) {
 // tp.seed, and its medium segment.  Returns whether it deposits.  The collimated projector takes
 // tvam_ray_world / tvam_segment_im (the ray records' own expressions), so that the export of such
 // a plan is the oracle's ray bit for bit.  RAY_ONLY: the world-space projector ray (r.o, r.d) alone,
-// for a caller that traces the vial itself (tvam_double.hip).  rng: the ray's generator, left after
-// the prefix for a caller whose path loop goes on drawing (tvam_insert.hip).
+// for a caller that traces the vial itself (WalkDouble, tvam_ray3d.h).  rng: the ray's generator, left after
+// the prefix for a caller whose path loop goes on drawing (WalkInsert, tvam_ray3d.h).
 template <int MESH = CN_NO_MESH, bool RAY_ONLY = false>
 __device__ __forceinline__ bool cn_ray_at(const TvamConsts& k, const TvamTiles& tp, int al, int colc, int rowc,
                                           uint64_t stream, ConeRay& r, TvamPcg& rng,

@@ -271,15 +271,13 @@ hipError_t tvam_launch_scatter_paths(int mode, const TvamConsts& k, const TvamTi
 // Forward of the scattered segments through brick bins (chunks of paths; host
 // syncs once per chunk to size the bins).  Returns hipErrorNotSupported when
 // the grid is too large for the packed records (callers then use the atomics).
-// writer: the record writer of another kind of segment (writer_slots records per path, forward
-// only: one for tvam_cone.hip's first segments, two for tvam_double.hip's) in place of
-// tvam_scatter_kernel<EMIT>; it fills sb.r / sb.m / sb.wmax of the paths [sb.p0, sb.p1) on `stream`
-// with `grid` workgroups of 256 threads (sb.m arrives zeroed: a slot it leaves alone is empty).
-typedef void (*TvamRecWriter)(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
-                              const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
+// walk: the first segments of a 3-D ray plan (TvamWalk below; forward only) in place of the scattered
+// ones: tvam_ray3d_write_records fills sb.r / sb.m / sb.wmax of the paths [sb.p0, sb.p1), one record
+// slot per possible segment, in place of tvam_scatter_kernel<EMIT> (sb.m arrives zeroed: a slot it
+// leaves alone is empty).
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
-                               hipStream_t stream, TvamRecWriter writer = nullptr, int writer_slots = 1);
+                               hipStream_t stream, int walk = -1);
 // the scratch back to its initial state: its event and pinned word here, the device memory with its owners
 void tvam_bin_scratch_free(TvamBinScratch& s);
 
@@ -299,38 +297,29 @@ hipError_t tvam_launch_general_paths(int mode, const TvamConsts& k, const TvamTi
 // 1 = brick bins, 0 = per-ray atomics.  Measured at 400^3 / 400 angles: the
 // binned forward takes 71 ms (41 ms from the bin cache), the per-ray atomics 1448 ms.
 #define TVAM_CONE_BINNED_DEFAULT 1
-// Telecentric / lens projectors (tvam_cone.hip): every ray's first medium segment is a 3-D ray.
+// 3-D ray plans (tvam_ray3d.hip): telecentric / lens projectors, 'custom', traced glass and
+// 'double_cylindrical' vials, dielectric occluders.  Every ray is traced in 3-D and deposits along
+// its medium segments; the plans differ in how the next segment is found, the walk (tvam_ray3d.h).
+//   TVAM_WALK_ONE     one segment (cn_ray_at: index matched, mesh interfaces or analytic glass by
+//                     cn_mesh_mode(k))
+//   TVAM_WALK_DOUBLE  'double_cylindrical': at most two, in front of the inner vial and behind it
+//   TVAM_WALK_INSERT  dielectric occluders: any number (k.mesh: the hierarchy over all inserts;
+//                     aux: device [n_tris] eta by caller-order triangle, null for the other walks)
+enum TvamWalk { TVAM_WALK_NONE = -1, TVAM_WALK_ONE = 0, TVAM_WALK_DOUBLE = 1, TVAM_WALK_INSERT = 2 };
+// record slots per path of the binned forward (0: unbounded, no binned forward)
+inline int tvam_walk_slots(int walk) { return walk == TVAM_WALK_ONE ? 1 : (walk == TVAM_WALK_DOUBLE ? 2 : 0); }
 // Per-ray kernels (forward: global atomics, `out` zeroed by the caller; adjoint: gathers, `out`
-// zeroed by the caller; count), the brick-bin record writer and the ray export.
-hipError_t tvam_launch_cone_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
-                                 const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
-                                 hipStream_t stream);
-void tvam_cone_write_records(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
-                             const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
-hipError_t tvam_launch_cone_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
-                                   hipStream_t stream);
-// 'double_cylindrical' vial (tvam_double.hip): every ray traced through the four tubes, at most two
-// medium segments per ray.  The per-ray kernels, the brick-bin record writer (two slots per path)
-// and the export of the rays (16 floats per ray, may be null) and of both segments ([2][8] floats
-// per ray, may be null).
-hipError_t tvam_launch_double_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
-                                   const int32_t* idxmap, const float* gin, float* out, unsigned long long* counter,
-                                   hipStream_t stream);
-void tvam_double_write_records(const TvamConsts& k, const TvamTiles& t, const float* pat, const int32_t* idxmap,
-                               const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
-hipError_t tvam_launch_double_export(const TvamConsts& k, const TvamTiles& t, const int32_t* idxmap, float* rays,
-                                     float* segs, hipStream_t stream);
-// Dielectric occluders (tvam_insert.hip): every ray walked through the container, the black
-// occluders and the inserts' triangles (k.mesh: the hierarchy over all of them; tri_eta: device
-// [n_tris] eta by caller-order triangle), any number of medium segments per ray.  The per-ray
-// kernels and the export of the rays (16 floats per ray, may be null) and of the segments
-// ([max_segments][8] floats and a count per ray, may both be null).
-hipError_t tvam_launch_insert_rays(int mode, const TvamConsts& k, const TvamTiles& t, const float* tri_eta,
-                                   const float* pat, const int32_t* idxmap, const float* gin, float* out,
-                                   unsigned long long* counter, hipStream_t stream);
-hipError_t tvam_launch_insert_export(const TvamConsts& k, const TvamTiles& t, const float* tri_eta,
-                                     const int32_t* idxmap, float* rays, float* segs, int32_t max_segments,
-                                     int32_t* nseg, hipStream_t stream);
+// zeroed by the caller; count), the brick-bin record writer (walks with slots) and the export of the
+// rays (16 floats per ray, may be null) and of the segments ([max_segments][8] floats per ray, may
+// be null, and a count per ray, may be null).
+hipError_t tvam_launch_ray3d(int mode, int walk, const TvamConsts& k, const TvamTiles& t, const float* aux,
+                             const float* pat, const int32_t* idxmap, const float* gin, float* out,
+                             unsigned long long* counter, hipStream_t stream);
+void tvam_ray3d_write_records(int walk, const TvamConsts& k, const TvamTiles& t, const float* pat,
+                              const int32_t* idxmap, const TvamSegBuf& sb, unsigned grid, hipStream_t stream);
+hipError_t tvam_launch_ray3d_export(int walk, const TvamConsts& k, const TvamTiles& t, const float* aux,
+                                    const int32_t* idxmap, float* rays, float* segs, int32_t max_segments,
+                                    int32_t* nseg, hipStream_t stream);
 // Extinction derivatives (tvam_dsigma.hip): one thread per (ray, sample) over the segment the plan's
 // forward marches (cone: a 3-D ray plan's cn_ray_at, else the collimated plans' planar first
 // segment).  FWD: the tangent film d dose / d sigma_t added into `tangent` (zeroed by the caller).

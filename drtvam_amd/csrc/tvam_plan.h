@@ -39,7 +39,7 @@ struct tvam_plan {
     bool cyl;    // refracting (cylindrical / square) vial: per-ray directions and weights
     bool surface = false;    // surface-aware film (2 channels): per-path kernels cut at the target mesh
     bool general = false;    // sample_time or a ratio / delta sensor: the general per-path kernel
-    bool cone = false;       // telecentric / lens projector: 3-D first segments (tvam_cone.hip); implies general
+    bool cone = false;       // telecentric / lens projector: 3-D first segments (tvam_ray3d.hip); implies general
     bool mesh = false;       // 'custom' vial: mesh interfaces traced per ray (tvam_mesh.h); implies cone
     const float* vols = nullptr;  // caller's compute_volume() output (tvam_plan_set_volumes)
     TvamDevBuf<float> tgt, occ;   // target mesh (surface-aware films) and occluder triangles
@@ -134,6 +134,17 @@ struct tvam_plan {
 inline bool tvam_cone_binned(const tvam_plan* p) {
     const int fl = p->desc.flags;
     return (fl & TVAM_FLAG_BIN_FIRST) || (!(fl & TVAM_FLAG_SCATTER_ATOMIC) && TVAM_CONE_BINNED_DEFAULT);
+}
+
+// the walk of a 3-D ray plan (p->cone; tvam_ray3d.h)
+inline int tvam_plan_walk(const tvam_plan* p) {
+    return p->ins ? TVAM_WALK_INSERT : (p->dbl ? TVAM_WALK_DOUBLE : TVAM_WALK_ONE);
+}
+
+// one medium segment as the host segment dumpers write it: o2[3], maxt, d2[3], att
+inline void seg_row(float* sg, const float o2[3], const float d2[3], float maxt, float att) {
+    sg[0] = o2[0], sg[1] = o2[1], sg[2] = o2[2], sg[3] = maxt;
+    sg[4] = d2[0], sg[5] = d2[1], sg[6] = d2[2], sg[7] = att;
 }
 
 // rays of the shard at one sample per pixel: a dense active set's length

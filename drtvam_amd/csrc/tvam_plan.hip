@@ -94,7 +94,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_traced: vial_type must be TVAM_VIAL_CYLINDRICAL or TVAM_VIAL_SQUARE (other vials: tvam_plan_create and its siblings)");
     if (inserts) {
         // dielectric occluders (tvam_plan_create_inserts): every ray walks the container, the black
-        // occluders and the inserts in 3-D and runs the per-ray kernels of tvam_insert.hip, whose
+        // occluders and the inserts in 3-D and runs the per-ray kernels of tvam_ray3d.hip, whose
         // limits these are (Russian roulette is honoured: no limit on rr_depth)
         auto no = [&](const char* what) {
             return tvam_fail(TVAM_ERR_UNSUPPORTED,
@@ -115,7 +115,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the interfaces)");
     } else if (d.vial_type == TVAM_VIAL_CUSTOM) {
         // mesh vial (tvam_plan_create_mesh): every ray is traced in 3-D through the interfaces and
-        // runs the per-ray kernels of tvam_cone.hip, whose limits these are
+        // runs the per-ray kernels of tvam_ray3d.hip, whose limits these are
         auto no = [&](const char* what) {
             return tvam_fail(TVAM_ERR_UNSUPPORTED,
                              std::string("a 'custom' vial with ") + what + " is not implemented on the GPU path");
@@ -136,7 +136,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
             return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs positive IORs");
     } else if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) {
         // two nested glass tubes (tvam_plan_create_double): every ray is traced in 3-D through the
-        // four interfaces and runs the per-ray kernels of tvam_double.hip, whose limits these are
+        // four interfaces and runs the per-ray kernels of tvam_ray3d.hip, whose limits these are
         auto no = [&](const char* what) {
             return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string("a 'double_cylindrical' vial with ") + what +
                                                   " is not implemented on the GPU path");
@@ -161,7 +161,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
     } else if (traced) {
         // glass tube or cuvette traced per ray (tvam_plan_create_traced): every ray is traced in 3-D
         // through the two analytic surfaces (tvam_glass.h) and runs the per-ray kernels of
-        // tvam_cone.hip, whose limits these are
+        // tvam_ray3d.hip, whose limits these are
         const char* pn = d.projector_type == TVAM_PROJECTOR_LENS          ? "'lens'"
                          : d.projector_type == TVAM_PROJECTOR_TELECENTRIC ? "'telecentric'"
                                                                           : "'collimated'";
@@ -185,7 +185,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
         if (d.rr_depth < 2) return no("rr_depth < 2 (Russian roulette before the medium segment)");
     } else if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
-        // 3-D projector rays (tvam_cone.hip): index-matched vial, absorbing medium, 'dda' sensor,
+        // 3-D projector rays (tvam_ray3d.hip): index-matched vial, absorbing medium, 'dda' sensor,
         // one-channel film, the whole film
         const char* pn = d.projector_type == TVAM_PROJECTOR_LENS ? "'lens'" : "'telecentric'";
         auto no = [&](const char* what) {
@@ -1381,9 +1381,7 @@ extern "C" int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* in
         float o2[3], d2[3], maxt, att;
         while (tvam_insert_next(k, sc, u != nullptr, dr, w, o2, d2, maxt, att)) {
             if (s < max_segments) {
-                float* sg = row + 8 * s;
-                sg[0] = o2[0], sg[1] = o2[1], sg[2] = o2[2], sg[3] = maxt;
-                sg[4] = d2[0], sg[5] = d2[1], sg[6] = d2[2], sg[7] = att;
+                seg_row(row + 8 * s, o2, d2, maxt, att);
             }
             ++s;
         }
@@ -1430,8 +1428,7 @@ extern "C" int tvam_traced_segments(const tvam_desc* desc, const float* o, const
         float o2[3], d2[3], maxt, att;
         float* s = segs + 8 * i;
         if (tvam_segment_traced(k, o + 3 * i, d + 3 * i, o2, d2, maxt, att)) {
-            s[0] = o2[0], s[1] = o2[1], s[2] = o2[2], s[3] = maxt;
-            s[4] = d2[0], s[5] = d2[1], s[6] = d2[2], s[7] = att;
+            seg_row(s, o2, d2, maxt, att);
         } else {
             for (int j = 0; j < 8; ++j) s[j] = 0.0f;
         }

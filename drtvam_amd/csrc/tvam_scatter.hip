@@ -194,11 +194,7 @@ __global__ __launch_bounds__(256) void tvam_scatter_kernel(TvamConsts k, TvamTil
                 SegDda q;
                 if (seg <= sb.slots && sc_dda_init(k, o, dv, tsi, q)) {
                     const int64_t slot = (i - sb.p0) * sb.slots + (seg - 1);
-                    sb.r[TVAM_REC_F4 * slot] = make_float4(q.t_start, q.tau_end, q.dtm0[0], q.dtm0[1]);
-                    sb.r[TVAM_REC_F4 * slot + 1] = make_float4(q.dtm0[2], q.ts[0] * (float)q.step[0], q.ts[1] * (float)q.step[1],
-                                             q.ts[2] * (float)q.step[2]);
-                    // .z: the attenuation alone, for the cached forward's rescale (tvam_bin_reweight_kernel)
-                    sb.r[TVAM_REC_F4 * slot + 2] = make_float4(__int_as_float(q.sv[0] | (q.sv[1] << 11) | (q.sv[2] << 22)), em * att, att, 0.0f);
+                    sc_pack(sb, slot, q, em * att, att);
                     // the bricks it crosses: counted in closed form (the bin fill does the only walk),
                     // or walked when the counting sort needs each brick's count
                     sb.m[slot] = hist ? (uint32_t)sc_walk_bricks(k, q, [&](int bid, float, float) {
@@ -791,24 +787,7 @@ hipError_t tvam_launch_scatter_paths(int mode, const TvamConsts& k, const TvamTi
 
 namespace {
 
-__device__ __forceinline__ void sc_unpack(const float4 a, const float4 b, const float4 cf, SegDda& q, float& w) {
-    const int2 c = make_int2(__float_as_int(cf.x), __float_as_int(cf.y));
-    q.t_start = a.x;
-    q.tau_end = a.y;
-    q.dtm0[0] = a.z;
-    q.dtm0[1] = a.w;
-    q.dtm0[2] = b.x;
-    const float tsv[3] = {b.y, b.z, b.w};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        q.step[i] = tsv[i] < 0.0f ? -1 : 1;
-        q.ts[i] = fabsf(tsv[i]);
-    }
-    q.sv[0] = c.x & 0x7ff;
-    q.sv[1] = (c.x >> 11) & 0x7ff;
-    q.sv[2] = (c.x >> 22) & 0x3ff;
-    w = __int_as_float(c.y);
-}
+// sc_pack, sc_unpack: tvam_seg3d.h
 
 // (brick, entry) pairs; an entry is one (segment, brick) crossing, entries of
 // a segment are contiguous from off[slot].  The value is the segment slot.
@@ -1302,7 +1281,8 @@ void tvam_bin_scratch_free(TvamBinScratch& s) {
 
 hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t, const float* pat,
                                const int32_t* idxmap, const float* gin, float* out, TvamBinScratch& s,
-                               hipStream_t stream, TvamRecWriter writer, int writer_slots) {
+                               hipStream_t stream, int walk) {
+    const bool writer = walk != TVAM_WALK_NONE;
     for (int i = 0; i < 5; ++i) s.st[i] = 0;  // stats of this call, also when it bins nothing
     // an earlier call's count check, if its copy has landed: a slot whose brick walk disagreed with
     // the writer's closed-form count (never, by construction) may have dropped entries -- fail loudly
@@ -1312,9 +1292,9 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
     }
     const int nsurf = k.vial_type == 0 ? 1 : 2;
     // later medium segments per path; a record writer writes its own count per path
-    const int slots = writer ? writer_slots : k.max_depth - nsurf - 1;
+    const int slots = writer ? tvam_walk_slots(walk) : k.max_depth - nsurf - 1;
+    if (writer && (mode != TVAM_MODE_FWD || slots == 0)) return hipErrorNotSupported;  // (an unbounded walk has no record slots)
     if (slots <= 0) return hipSuccess;
-    if (writer && mode != TVAM_MODE_FWD) return hipErrorNotSupported;
     if (k.res[0] > 2048 || k.res[1] > 2048 || k.res[2] > 1024) return hipErrorNotSupported;
     const bool adj = mode == TVAM_MODE_ADJ;
     const int nbx = (k.res[0] + TVAM_BX - 1) / TVAM_BX, nby = (k.res[1] + TVAM_BY - 1) / TVAM_BY,
@@ -1460,7 +1440,7 @@ hipError_t tvam_scatter_binned(int mode, const TvamConsts& k, const TvamTiles& t
             sb.hist = nullptr;
         }
         if (writer)
-            writer(k, t, pat, idxmap, sb, (unsigned)g, stream);
+            tvam_ray3d_write_records(walk, k, t, pat, idxmap, sb, (unsigned)g, stream);
         else
             hipLaunchKernelGGL(tvam_scatter_kernel<TVAM_MODE_EMIT>, dim3((unsigned)g), dim3(256),
                                csort ? (size_t)nbricks * sizeof(uint32_t) : 0, stream, k, t, pat, idxmap, nullptr,

@@ -1,6 +1,6 @@
 // tvam_seg3d.h -- the 3-D medium segment shared by the scattered segments (tvam_scatter.hip) and the
-// first segment of the telecentric / lens projectors (tvam_cone.hip): the open-tube hit of a 3-D
-// ray and the per-ray DDA march (device only).
+// segments of the 3-D ray plans (tvam_ray3d.hip): the open-tube hit of a 3-D ray, the per-ray DDA
+// march and the brick-bin record of a segment (device only).
 #pragma once
 #include "tvam_bricks.h"
 
@@ -113,6 +113,36 @@ __device__ float sc_dda(const TvamConsts& k, float ox, float oy, float oz, float
         ++nvis;
     });
     return acc;
+}
+
+// The brick-bin record of a segment (TvamSegBuf: 3 float4 per slot), written by the record writers
+// (tvam_scatter_kernel<EMIT>, tvam_ray3d_emit_kernel) and read back by the bin fill and the brick
+// march.  wgt: the record's weight; att: the path attenuation alone (.z, for the cached forward's
+// rescale, tvam_bin_reweight_kernel).
+__device__ __forceinline__ void sc_pack(const TvamSegBuf& sb, int64_t slot, const SegDda& q, float wgt, float att) {
+    sb.r[TVAM_REC_F4 * slot] = make_float4(q.t_start, q.tau_end, q.dtm0[0], q.dtm0[1]);
+    sb.r[TVAM_REC_F4 * slot + 1] = make_float4(q.dtm0[2], q.ts[0] * (float)q.step[0], q.ts[1] * (float)q.step[1],
+                                               q.ts[2] * (float)q.step[2]);
+    sb.r[TVAM_REC_F4 * slot + 2] = make_float4(__int_as_float(q.sv[0] | (q.sv[1] << 11) | (q.sv[2] << 22)), wgt, att, 0.0f);
+}
+
+__device__ __forceinline__ void sc_unpack(const float4 a, const float4 b, const float4 cf, SegDda& q, float& w) {
+    const int2 c = make_int2(__float_as_int(cf.x), __float_as_int(cf.y));
+    q.t_start = a.x;
+    q.tau_end = a.y;
+    q.dtm0[0] = a.z;
+    q.dtm0[1] = a.w;
+    q.dtm0[2] = b.x;
+    const float tsv[3] = {b.y, b.z, b.w};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        q.step[i] = tsv[i] < 0.0f ? -1 : 1;
+        q.ts[i] = fabsf(tsv[i]);
+    }
+    q.sv[0] = c.x & 0x7ff;
+    q.sv[1] = (c.x >> 11) & 0x7ff;
+    q.sv[2] = (c.x >> 22) & 0x3ff;
+    w = __int_as_float(c.y);
 }
 
 // The largest of a 256-thread workgroup's non-negative values into *dst (float bits, which order

@@ -551,7 +551,7 @@ int tvam_plan_set_volumes(tvam_plan* plan, const float* volumes);
    bit 0 = planar adjoint (regular sampling: one ray record per (angle,
    column), Z-slice-sharing adjoint); bit 1 = voxel-driven planar forward
    (straight rays only: not behind a refracting vial); bit 2 = 3-D projector
-   rays (telecentric / lens: tvam_cone.hip; ABI v13). */
+   rays (telecentric / lens: tvam_ray3d.hip; ABI v13). */
 int tvam_plan_path(const tvam_plan* plan);
 
 /* Diagnostics: the instantiation of the voxel-driven forward kernel that the plan launches (the

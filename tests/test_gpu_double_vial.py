@@ -1,4 +1,4 @@
-"""The 'double_cylindrical' vial on the GPU (tvam_double.h, tvam_double.hip): every ray traced
+"""The 'double_cylindrical' vial on the GPU (tvam_double.h, tvam_ray3d.hip): every ray traced
 through four dielectric tubes, up to two medium segments per ray.
 
 The oracle has no such vial, so the path is pinned the way tests/test_gpu_mesh_vial.py pins the

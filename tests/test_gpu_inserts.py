@@ -1,4 +1,4 @@
-"""Dielectric occluders on the GPU (tvam_insert.h, tvam_insert.hip): every ray walked through the
+"""Dielectric occluders on the GPU (tvam_insert.h, tvam_ray3d.hip): every ray walked through the
 container, the black occluders and the inserts' triangles, any number of medium segments per ray.
 
 The oracle knows only black occluders, so the path is pinned by the float64 model of

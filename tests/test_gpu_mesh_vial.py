@@ -1,4 +1,4 @@
-"""The 'custom' vial on the GPU (tvam_mesh.h, tvam_cone.hip): two dielectric triangle meshes, every
+"""The 'custom' vial on the GPU (tvam_mesh.h, tvam_ray3d.hip): two dielectric triangle meshes, every
 ray traced through them in 3-D by closest-hit queries against a bounding volume hierarchy.
 
 The oracle has no mesh vial, so the path is pinned the way tests/test_gpu_projectors.py pins the

@@ -1,4 +1,4 @@
-"""Telecentric and lens projectors on the GPU (tvam_cone.hip): the 3-D projector rays, their
+"""Telecentric and lens projectors on the GPU (tvam_ray3d.hip): the 3-D projector rays, their
 medium segments, the per-ray forward / adjoint / visit count and the brick-binned forward.
 
 The oracle restates only the collimated projector, so the new path is pinned in two steps:

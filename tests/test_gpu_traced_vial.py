@@ -1,5 +1,5 @@
 """The 'cylindrical' and 'square' vials traced per ray in 3-D on the GPU (tvam_glass.h, the CN_GLASS
-instantiations of tvam_cone.hip; plans of tvam_plan_create_traced).
+instantiations of tvam_ray3d.hip; plans of tvam_plan_create_traced).
 
   1. tvam_plan_rays (Projection.rays) against the float64 model of tests/traced_vial_model.py on
      every ray whose decisions the model finds at least 1e-4 from flipping (at most 1 % are not:

@@ -1,5 +1,5 @@
 // Stand-alone host run of the traced glass vials' tracer (drtvam_amd/csrc/tvam_glass.h: the code the
-// CN_GLASS kernels of tvam_cone.hip run), for a sanitizer build without a GPU or an interpreter:
+// CN_GLASS kernels of tvam_ray3d.hip run), for a sanitizer build without a GPU or an interpreter:
 //   hipcc --cuda-host-only -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //         -Iinclude tools/glass_check.hip -o glass_check && ./glass_check
 // Vials: the tests' tube (r_ext 6.5 / r_int 6.0) and cuvette (w_ext 13 / w_int 12), height 4, glass
