@@ -44,6 +44,10 @@ FLAG_BIN_FIRST = 32
 LBFGS_WORK_DOUBLES = 2048 * 64
 LOSS_KIND_THRESHOLD = 0
 LOSS_KIND_L2 = 1
+DPROJ_DISTANCE = 0
+DPROJ_FOCUS_DISTANCE = 1
+DPROJ_APERTURE_RADIUS = 2
+DPROJ_PIXEL_SIZE = 3
 
 
 class TvamDoubleVial(ctypes.Structure):
@@ -224,6 +228,10 @@ EXPORTS = {
     "tvam_forward_dsigma": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_adjoint_dsigma": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_dsigma_weights": (ctypes.c_int, [ctypes.c_float, _P, _P, ctypes.c_int64, _P]),
+    "tvam_forward_dprojector": (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.c_uint32, _P, _P]),
+    "tvam_adjoint_dprojector": (ctypes.c_int, [_P, ctypes.c_int32, _P, _P, _P, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.c_uint32, _P, _P]),
     "tvam_forward_slices": (ctypes.c_int, [_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                            ctypes.c_int32, ctypes.c_int32, _P, _P]),
     "tvam_plan_fwd_chunk": (ctypes.c_int, [_P]),

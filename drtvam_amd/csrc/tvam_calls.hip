@@ -4,6 +4,8 @@
 // path uses a lazily allocated dense scratch, and the per-ray kernels their cached ray records.
 #include "tvam_plan.h"
 
+#include "tvam_dproj.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -518,6 +520,85 @@ extern "C" int tvam_adjoint_dsigma(tvam_plan* p, const float* active_data, const
     e = tvam_launch_dsigma(TVAM_MODE_ADJ, p->cone, k, t, pat, idxmap, grad_dose, nullptr, p->dsig_part.get(), g_sigma,
                            stream);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "extinction gradient launch");
+}
+
+// Projector derivatives (tvam_dproj.hip).  What both entries refuse, from the descriptor and the
+// plan's flags alone: no device call, nothing allocated.
+static int dproj_check(const tvam_plan* p, int32_t param, const char* who) {
+    const tvam_desc& d = p->desc;
+    const char* why = nullptr;
+    std::string vial;
+    if (p->ins) why = "a plan with dielectric occluders (inserts)";
+    else if (p->dbl) why = "a 'double_cylindrical' vial";
+    else if (p->mesh) why = "a 'custom' vial";
+    else if (d.vial_type != TVAM_VIAL_INDEX_MATCHED) {
+        vial = std::string(p->traced ? "a traced '" : "a '") + (d.vial_type == TVAM_VIAL_SQUARE ? "square" : "cylindrical") +
+               "' vial";
+        why = vial.c_str();
+    } else if (d.albedo > 0.0f) why = "albedo > 0 (a scattering medium)";
+    else if (d.sensor_type != TVAM_SENSOR_DDA) why = "the 'ratio' / 'delta' sensors are not differentiated";
+    else if (p->surface) why = "a surface-aware (two-channel) film is not differentiated";
+    else if (p->k.z0 != 0 || p->k.nz != p->k.res[2]) why = "a film slab is not differentiated (render the whole film)";
+    else if (d.n_occluder_tris > 0) why = "occluders";
+    else if (d.projector_type != TVAM_PROJECTOR_TELECENTRIC && d.projector_type != TVAM_PROJECTOR_LENS)
+        why = "a collimated projector (telecentric and lens projectors only)";
+    if (why) return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": " + why);
+    if (param < TVAM_DPROJ_DISTANCE || param > TVAM_DPROJ_PIXEL_SIZE)
+        return tvam_fail(TVAM_ERR_INVALID, std::string(who) + ": param must be one of TVAM_DPROJ_*");
+    return 0;
+}
+
+static TvamDproj dproj_of(const tvam_plan* p, int32_t param) {
+    return TvamDproj{param, p->desc.pixel_size_x, p->desc.pixel_size_y};
+}
+
+extern "C" int tvam_forward_dprojector(tvam_plan* p, int32_t param, const float* active_data,
+                                       const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                                       float* tangent, void* stream_) {
+    if (!p || !tangent || (!active_data && n_active))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_forward_dprojector: null argument");
+    int rc = dproj_check(p, param, "tvam_forward_dprojector");
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    TvamConsts k;
+    if ((rc = call_setup(p, n_active, active_pixels, spp, k))) return rc;
+    const size_t V = (size_t)k.res[0] * k.res[1] * k.nz;
+    hipError_t e = hipMemsetAsync(tangent, 0, V * sizeof(float), stream);
+    if (e != hipSuccess) return tvam_hip_fail(e, "hipMemsetAsync");
+    if (p->empty || n_active == 0) return 0;
+    const float* pat = active_data;
+    const int32_t* idxmap = nullptr;
+    if ((rc = bind_active(p, k, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
+    e = tvam_launch_dproj(TVAM_MODE_FWD, k, call_tiles(p, spp, seed), dproj_of(p, param), pat, idxmap, nullptr, tangent,
+                          nullptr, nullptr, stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "projector tangent launch");
+}
+
+extern "C" int tvam_adjoint_dprojector(tvam_plan* p, int32_t param, const float* active_data, const float* grad_dose,
+                                       const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                                       double* g, void* stream_) {
+    if (!p || !grad_dose || !g || (!active_data && n_active))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_adjoint_dprojector: null argument");
+    int rc = dproj_check(p, param, "tvam_adjoint_dprojector");
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    TvamConsts k;
+    if ((rc = call_setup(p, n_active, active_pixels, spp, k))) return rc;
+    hipError_t e;
+    if (p->empty || n_active == 0) {
+        e = hipMemsetAsync(g, 0, sizeof(double), stream);
+        return e == hipSuccess ? 0 : tvam_hip_fail(e, "hipMemsetAsync");
+    }
+    const float* pat = active_data;
+    const int32_t* idxmap = nullptr;
+    if ((rc = bind_active(p, k, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
+    const TvamTiles t = call_tiles(p, spp, seed);
+    // (the grid, and with it the order of the sum, depends on the ray count alone)
+    if ((e = p->dsig_part.grow(tvam_dsigma_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp))) != hipSuccess)
+        return tvam_hip_fail(e, "hipMalloc (projector partials)");
+    e = tvam_launch_dproj(TVAM_MODE_ADJ, k, t, dproj_of(p, param), pat, idxmap, grad_dose, nullptr, p->dsig_part.get(), g,
+                          stream);
+    return e == hipSuccess ? 0 : tvam_hip_fail(e, "projector gradient launch");
 }
 
 // The rays of a call (tvam_ray3d.hip's export serves every projector kind); `segs`: the medium

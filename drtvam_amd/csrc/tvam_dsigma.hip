@@ -110,6 +110,11 @@ void ds_launch(int mode, const TvamConsts& k, const TvamTiles& t, const float* p
 
 unsigned tvam_dsigma_grid(int64_t n_rays) { return tvam_grid_1d(n_rays, 2048); }
 
+hipError_t tvam_launch_partial_sum(const double* partials, int n, double* out, hipStream_t stream) {
+    hipLaunchKernelGGL(tvam_dsigma_sum_kernel, dim3(1), dim3(256), 0, stream, partials, n, out);
+    return hipGetLastError();
+}
+
 hipError_t tvam_launch_dsigma(int mode, bool cone, const TvamConsts& k, const TvamTiles& t, const float* pat,
                               const int32_t* idxmap, const float* gin, float* tangent, double* partials,
                               double* g_sigma, hipStream_t stream) {
@@ -125,10 +130,7 @@ hipError_t tvam_launch_dsigma(int mode, bool cone, const TvamConsts& k, const Tv
         }
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && mode == TVAM_MODE_ADJ) {
-        hipLaunchKernelGGL(tvam_dsigma_sum_kernel, dim3(1), dim3(256), 0, stream, partials, (int)grid, g_sigma);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess && mode == TVAM_MODE_ADJ) e = tvam_launch_partial_sum(partials, (int)grid, g_sigma, stream);
     return e;
 }
 

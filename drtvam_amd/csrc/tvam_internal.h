@@ -326,6 +326,8 @@ hipError_t tvam_launch_ray3d_export(int walk, const TvamConsts& k, const TvamTil
 // ADJ: sum_v gin[v] * tangent[v] into g_sigma[0] (device, overwritten) through `partials`, one fp64
 // partial per workgroup of the launch's grid (tvam_dsigma_grid of the ray count); no atomics.
 unsigned tvam_dsigma_grid(int64_t n_rays);
+// the n per-workgroup partials of such a launch into out[0] in a fixed order (one workgroup)
+hipError_t tvam_launch_partial_sum(const double* partials, int n, double* out, hipStream_t stream);
 hipError_t tvam_launch_dsigma(int mode, bool cone, const TvamConsts& k, const TvamTiles& t, const float* pat,
                               const int32_t* idxmap, const float* gin, float* tangent, double* partials,
                               double* g_sigma, hipStream_t stream);

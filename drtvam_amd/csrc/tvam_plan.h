@@ -101,7 +101,7 @@ struct tvam_plan {
     // sparse scratch (dense crop layout), allocated on first sparse call
     TvamDevBuf<float> dense;
     TvamDevBuf<int32_t> idxmap;
-    TvamDevBuf<double> dsig_part;  // tvam_adjoint_dsigma: one partial per workgroup, allocated on its first call
+    TvamDevBuf<double> dsig_part;  // tvam_adjoint_dsigma / tvam_adjoint_dprojector: one partial per workgroup, allocated on the first call
 
     // the kernel structs' table pointers (k, tiles, pl) from their owners; an owner that holds
     // nothing gives nullptr.  (pl.chord and the visit lists' pl.adjl_* are set by their builders.)

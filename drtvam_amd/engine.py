@@ -37,6 +37,15 @@ def derive_seed_grad(seed: int) -> int:
     return v0
 
 
+DPROJ_PARAMS = {'distance': _abi.DPROJ_DISTANCE, 'focus_distance': _abi.DPROJ_FOCUS_DISTANCE,
+                'aperture_radius': _abi.DPROJ_APERTURE_RADIUS, 'pixel_size': _abi.DPROJ_PIXEL_SIZE}
+
+
+def dproj_id(param) -> int:
+    """A projector parameter (its name or _abi.DPROJ_*) as the id the library takes."""
+    return DPROJ_PARAMS[param] if isinstance(param, str) else int(param)
+
+
 class Projection:
     """One tvam_plan (scene tables) bound to one GPU."""
 
@@ -186,6 +195,42 @@ class Projection:
         with torch.cuda.device(self.device):
             _abi.check(self.lib.tvam_adjoint_dsigma(
                 self._plan, active_data.data_ptr(), grad_dose.data_ptr(),
+                None if active_pixels is None else active_pixels.data_ptr(), active_data.numel(), spp,
+                seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    def forward_dprojector(self, param, active_data: torch.Tensor, active_pixels: Optional[torch.Tensor] = None,
+                           spp: int = 1, seed: int = 0) -> torch.Tensor:
+        """The tangent film d dose / d theta of forward(active_data, ...) in one projector parameter
+        (tvam_forward_dprojector), film shaped.  param: _abi.DPROJ_* or its name ('distance',
+        'focus_distance', 'aperture_radius', 'pixel_size').  Telecentric / lens plans behind the
+        index-matched vial; ValueError names what the entry refuses."""
+        self._check_tensor(active_data, torch.float32, "active_data")
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+        out = torch.empty(self.film_shape, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_forward_dprojector(
+                self._plan, dproj_id(param), active_data.data_ptr(),
+                None if active_pixels is None else active_pixels.data_ptr(), active_data.numel(), spp,
+                seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
+        return out
+
+    def adjoint_dprojector(self, param, active_data: torch.Tensor, grad_dose: torch.Tensor,
+                           active_pixels: Optional[torch.Tensor] = None, spp: int = 1, seed: int = 0) -> torch.Tensor:
+        """d <grad_dose, forward(active_data, ...)> / d theta (tvam_adjoint_dprojector): a 0-dim float64
+        tensor, the same bits for the same call."""
+        self._check_tensor(active_data, torch.float32, "active_data")
+        grad_dose = grad_dose.contiguous()
+        self._check_tensor(grad_dose, torch.float32, "grad_dose")
+        if grad_dose.numel() != self.film_shape[0] * self.film_shape[1] * self.film_shape[2] * self.film_shape[3]:
+            raise ValueError("grad_dose has the wrong number of elements")
+        if active_pixels is not None:
+            self._check_pixels(active_pixels)
+        out = torch.empty((), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.tvam_adjoint_dprojector(
+                self._plan, dproj_id(param), active_data.data_ptr(), grad_dose.data_ptr(),
                 None if active_pixels is None else active_pixels.data_ptr(), active_data.numel(), spp,
                 seed & 0xFFFFFFFF, out.data_ptr(), _stream_ptr(self.device)))
         return out
@@ -430,20 +475,26 @@ class Projection:
 
 
 class TvamRender(torch.autograd.Function):
-    """dose = render(active_data); d loss / d active_data via the adjoint kernel, and d loss / d sigma_t
-    via the extinction-gradient kernel when the medium's sigma_t is an input that requires grad."""
+    """dose = render(active_data); d loss / d active_data via the adjoint kernel, d loss / d sigma_t via
+    the extinction-gradient kernel when the medium's sigma_t is an input that requires grad, and
+    d loss / d (a projector parameter) via the projector-gradient kernel for the inputs `thetas`:
+    dproj[i] = [(parameter, coefficient)], the library's derivatives that make up d / d thetas[i]."""
 
     @staticmethod
     def forward(ctx, active_data, proj: Projection, active_pixels, spp: int, spp_grad: int, seed: int,
-                seed_grad: int, sigma_t=None):
+                seed_grad: int, sigma_t=None, dproj=(), *thetas):
         ctx.proj = proj
         ctx.active_pixels = active_pixels
         ctx.spp_grad = spp_grad
         ctx.seed_grad = seed_grad
         ctx.n_active = active_data.numel()
+        ctx.dproj = dproj
+        ctx.theta_like = [(t.device, t.dtype) for t in thetas]
         data = active_data.detach().contiguous()
-        if sigma_t is not None and sigma_t.requires_grad:  # the sigma gradient renders the patterns again
+        need_sigma = sigma_t is not None and sigma_t.requires_grad
+        if need_sigma or any(t.requires_grad for t in thetas):  # these gradients render the patterns again
             ctx.save_for_backward(data)
+        if need_sigma:
             ctx.sigma_like = (sigma_t.device, sigma_t.dtype)
         return proj.forward(data, active_pixels, spp, seed)
 
@@ -458,14 +509,26 @@ class TvamRender(torch.autograd.Function):
             (data,) = ctx.saved_tensors
             gs = ctx.proj.adjoint_dsigma(data, grad_dose, ctx.active_pixels, ctx.spp_grad, ctx.seed_grad)
             gs = gs.to(device=ctx.sigma_like[0], dtype=ctx.sigma_like[1])
-        return g, None, None, None, None, None, None, gs
+        gt = []
+        for i, terms in enumerate(ctx.dproj):
+            if not ctx.needs_input_grad[9 + i]:
+                gt.append(None)
+                continue
+            (data,) = ctx.saved_tensors
+            gi = sum(c * ctx.proj.adjoint_dprojector(param, data, grad_dose, ctx.active_pixels, ctx.spp_grad, ctx.seed_grad)
+                     for param, c in terms)
+            gt.append(gi.to(device=ctx.theta_like[i][0], dtype=ctx.theta_like[i][1]))
+        return (g, None, None, None, None, None, None, gs, None, *gt)
 
 
 def render(proj: Projection, active_data: torch.Tensor, active_pixels: Optional[torch.Tensor] = None,
            spp: int = 1, spp_grad: Optional[int] = None, seed: int = 0, seed_grad: Optional[int] = None,
-           sigma_t: Optional[torch.Tensor] = None):
+           sigma_t: Optional[torch.Tensor] = None, projector=()):
     """sigma_t: the medium's extinction as a 0-dim tensor, an input of the render when it requires
-    grad.  The plan bakes sigma_t in, so the tensor must hold the plan's own value (as float32)."""
+    grad.  The plan bakes sigma_t in, so the tensor must hold the plan's own value (as float32).
+    projector: [(theta, [(parameter, coefficient), ...])], 0-dim tensors that are inputs of the render
+    when they require grad, each with the projector derivatives (Projection.adjoint_dprojector) whose
+    weighted sum is d / d theta; the plan bakes the projector in as well, the caller keeps the two in step."""
     spp_grad = spp if spp_grad is None else spp_grad
     seed_grad = derive_seed_grad(seed) if seed_grad is None else seed_grad
     if sigma_t is not None:
@@ -475,7 +538,11 @@ def render(proj: Projection, active_data: torch.Tensor, active_pixels: Optional[
         if have != ctypes.c_float(proj.desc.sigma_t).value:
             raise ValueError(f"render: sigma_t = {have!r} is not the plan's extinction {proj.desc.sigma_t!r}; "
                              "build the Projection from a descriptor with this sigma_t")
-    return TvamRender.apply(active_data, proj, active_pixels, spp, spp_grad, seed, seed_grad, sigma_t)
+    for theta, _ in projector:
+        if theta.dim() != 0:
+            raise ValueError("render: a projector parameter must be a 0-dim tensor")
+    return TvamRender.apply(active_data, proj, active_pixels, spp, spp_grad, seed, seed_grad, sigma_t,
+                            tuple(terms for _, terms in projector), *[theta for theta, _ in projector])
 
 
 def target_mask(target: torch.Tensor) -> torch.Tensor:

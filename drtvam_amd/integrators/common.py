@@ -30,7 +30,7 @@ class TVAMIntegrator:
         self.tile = props.get('tile', 0)
         self.flags = props.get('flags', 0)
         self._plans = {}
-        self._families = {}  # descriptor with sigma_t blanked -> its one key in _plans
+        self._families = {}  # descriptor with sigma_t (and a telecentric / lens projector's calibration) blanked -> its one key in _plans
 
     def parse_scene(self, scene):
         if scene.container is None:
@@ -81,10 +81,13 @@ class TVAMIntegrator:
         key = (bytes(memoryview(ctypes.string_at(ctypes.addressof(d), ctypes.sizeof(d)))), beside, str(dev))
         proj = self._plans.get(key)
         if proj is None:
-            # a fit of the extinction builds a plan per step: plans whose descriptors differ in
-            # sigma_t alone evict one another
+            # a fit of the extinction or of a telecentric / lens projector's calibration builds a plan
+            # per step: plans whose descriptors differ in these fields alone evict one another
             fam = d.copy()
             fam.sigma_t = 0.0
+            if d.projector_type != _abi.PROJECTOR_COLLIMATED:
+                fam.distance = fam.focus_distance = fam.aperture_radius = 0.0
+                fam.pixel_size_x = fam.pixel_size_y = 0.0
             fam = (bytes(memoryview(ctypes.string_at(ctypes.addressof(fam), ctypes.sizeof(fam)))), beside, str(dev))
             old = self._families.pop(fam, None)
             if old is not None:

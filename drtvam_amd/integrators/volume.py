@@ -20,6 +20,14 @@ def _sigma_param(scene):
     return getattr(scene, 'sigma_t_param', None)
 
 
+def _projector_params(scene):
+    """[(name, tensor, [(parameter, coefficient)])] of traverse(scene)'s projector calibration that
+    requires grad (telecentric / lens projectors): the tensor and the library derivatives that sum to
+    d / d name (TVAMProjector.dproj_terms)."""
+    return [(name, t, scene.projector.dproj_terms(name))
+            for name, t in getattr(scene, 'projector_params', {}).items() if t.requires_grad]
+
+
 def _check_projectors(scene):
     if scene.projector is None:
         raise Exception("No projector found in the scene")
@@ -61,7 +69,8 @@ class VolumeIntegrator(TVAMIntegrator):
     def render_differentiable(self, scene, sensor=0, spp: int = 0, spp_grad: Optional[int] = None, seed: int = 0,
                               seed_grad: Optional[int] = None, active_data: Optional[torch.Tensor] = None):
         """mi.render with AD: dose depends differentiably on active_data (default: projector.active_data)
-        and, when traverse(scene)'s 'printing_medium.sigma_t' requires grad, on the medium's extinction."""
+        and, when traverse(scene)'s 'printing_medium.sigma_t' or 'projector.<calibration>' require grad, on
+        the medium's extinction and the projector's parameters."""
         _check_projectors(scene)
         sensor = self._sensor(scene, sensor)
         projector = scene.projector
@@ -74,11 +83,12 @@ class VolumeIntegrator(TVAMIntegrator):
         if sig is not None and not sig.requires_grad:
             sig = None
         return engine_render(proj, x, pix, spp, spp_grad, seed, derive_seed_grad(seed) if seed_grad is None else seed_grad,
-                             sigma_t=sig)
+                             sigma_t=sig, projector=[(t, terms) for _, t, terms in _projector_params(scene)])
 
     def render_forward(self, scene, params=None, sensor=0, seed: int = 0, spp: int = 0,
                        tangent: Optional[torch.Tensor] = None,
-                       tangent_sigma_t: Optional[float] = None) -> torch.Tensor:
+                       tangent_sigma_t: Optional[float] = None,
+                       tangent_projector: Optional[dict] = None) -> torch.Tensor:
         """Forward-mode derivative (volume.py:58-95): the dose tangent [Z, Y, X, C] produced by a
         tangent of projector.active_data.  The render is linear in the patterns, so this is the
         forward projection of the tangent (the reference propagates dr.grad(active_data) through
@@ -86,13 +96,16 @@ class VolumeIntegrator(TVAMIntegrator):
         defaults to projector.active_data.grad, the slot the reference reads it from.
         `tangent_sigma_t`: a tangent of the medium's extinction (sensor.py:371-375); the result is
         A tangent + tangent_sigma_t T with T = d dose / d sigma_t of projector.active_data
-        (Projection.forward_dsigma).  Either tangent alone is allowed."""
+        (Projection.forward_dsigma).  `tangent_projector`: tangents of traverse(scene)'s projector
+        calibration by name, e.g. {'focus_distance': 1.0}; each adds its tangent times
+        d dose / d name (Projection.forward_dprojector; a lens given by fov through the chain rule of
+        TVAMProjector.dproj_terms).  Any tangent alone is allowed."""
         _check_projectors(scene)
         sensor = self._sensor(scene, sensor)
         projector = scene.projector
         if tangent is None:
             tangent = projector.active_data.grad
-        if tangent is None and tangent_sigma_t is None:
+        if tangent is None and tangent_sigma_t is None and not tangent_projector:
             raise ValueError("render_forward: no tangent (set projector.active_data.grad or pass `tangent`)")
         if tangent is not None and tangent.numel() != projector.active_size():
             raise ValueError("render_forward: the tangent must have one entry per active pixel")
@@ -107,6 +120,11 @@ class VolumeIntegrator(TVAMIntegrator):
                 T = proj.forward_dsigma(projector.active_data.detach().contiguous(), pix, spp, seed)
                 T *= float(tangent_sigma_t)
                 out = T if out is None else out.add_(T)
+            for name, tv in (tangent_projector or {}).items():
+                for param, c in projector.dproj_terms(name):
+                    T = proj.forward_dprojector(param, projector.active_data.detach().contiguous(), pix, spp, seed)
+                    T *= float(tv) * c
+                    out = T if out is None else out.add_(T)
             return out
 
     def render_backward(self, scene, params, grad_in: torch.Tensor, sensor=0, seed: int = 0, spp: int = 0) -> None:
@@ -130,6 +148,13 @@ class VolumeIntegrator(TVAMIntegrator):
                 sig.grad = gs
             else:
                 sig.grad += gs
+        for _, t, terms in _projector_params(scene):
+            gt = sum(c * proj.adjoint_dprojector(param, x.detach().contiguous(), grad_in.contiguous(), pix, spp, seed)
+                     for param, c in terms).to(device=t.device, dtype=t.dtype)
+            if t.grad is None:
+                t.grad = gt
+            else:
+                t.grad += gt
 
 
 integrators = {'volume': VolumeIntegrator}

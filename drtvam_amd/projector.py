@@ -224,6 +224,25 @@ class TelecentricProjector(TVAMProjector):
         desc.aperture_radius = self.aperture_radius
         desc.focus_distance = self.focus_distance
 
+    # traverse(scene)'s differentiable parameters: name -> value
+    def calibration(self):
+        return {'distance': float(self.motion.distance), 'focus_distance': self.focus_distance,
+                'aperture_radius': self.aperture_radius, 'pixel_size': self.pixel_size[0]}
+
+    def set_calibration(self, values):
+        """Writes traverse(scene)'s values back and re-derives what depends on them ('pixel_size' moves both
+        pixel sizes by the same amount)."""
+        self.motion.distance = float(values['distance'])
+        self.focus_distance = float(values['focus_distance'])
+        self.aperture_radius = float(values['aperture_radius'])
+        shift = float(values['pixel_size']) - self.pixel_size[0]
+        self.pixel_size = (self.pixel_size[0] + shift, self.pixel_size[1] + shift)
+        self.emitter_size = (self.res[0] * self.pixel_size[0], self.res[1] * self.pixel_size[1])
+
+    def dproj_terms(self, name):
+        """d / d `name` as a sum of the library's derivatives: [(parameter, coefficient)]."""
+        return [(name, 1.0)]
+
     def to_string(self):
         return 'TelecentricProjector'
 
@@ -241,15 +260,53 @@ class LensProjector(TVAMProjector):
 
         assert not ('fov' in props and 'pixel_size' in props), "Specify either 'fov' or 'pixel_size', not both."
         assert ('fov' in props or 'pixel_size' in props), "Either 'fov' or 'pixel_size' must be specified."
-        if 'fov' in props:
+        self.by_fov = 'fov' in props
+        if self.by_fov:
             self.fov = float(props['fov'])
+        else:
+            self.pixel_size = float(props['pixel_size'])
+        self._derive()
+
+    def _derive(self):
+        """pixel_size from fov or fov from pixel_size, whichever the projector was configured by, and
+        the image area."""
+        if self.by_fov:
             # pixel_size * N_x = tan(fov / 2) * 2 * focus_distance (projector.py:254-255), in double
             self.pixel_size = float(np.tan(np.deg2rad(self.fov) / 2) * 2 * self.focus_distance / self.res[0])
-        if 'pixel_size' in props:
-            self.pixel_size = float(props['pixel_size'])
+        else:
             self.fov = float(np.rad2deg(2 * np.arctan(self.pixel_size * self.res[0] / 2 / self.focus_distance)))
         # image rectangle on the plane z = 1 (projector.py:267-271)
         self.area = (self.pixel_size / self.focus_distance) ** 2 * self.res[0] * self.res[1]
+
+    # traverse(scene)'s differentiable parameters (DESIGN.md section 4n): name -> value
+    def calibration(self):
+        v = {'distance': float(self.motion.distance), 'focus_distance': self.focus_distance,
+             'aperture_radius': self.aperture_radius}
+        v['fov' if self.by_fov else 'pixel_size'] = self.fov if self.by_fov else self.pixel_size
+        return v
+
+    def set_calibration(self, values):
+        """Writes traverse(scene)'s values back and re-derives what depends on them (the pixel size
+        of a lens given by fov, else the fov; the image area)."""
+        self.motion.distance = float(values['distance'])
+        self.focus_distance = float(values['focus_distance'])
+        self.aperture_radius = float(values['aperture_radius'])
+        if self.by_fov:
+            self.fov = float(values['fov'])
+        else:
+            self.pixel_size = float(values['pixel_size'])
+        self._derive()
+
+    def dproj_terms(self, name):
+        """d / d `name` as a sum of the library's derivatives: [(parameter, coefficient)].  By fov,
+        p = 2 F tan(fov / 2) / res_x moves with F and with fov: d / dF = d_F + (p / F) d_p and
+        d / dfov (degrees) = (pi / 180) F sec^2(fov / 2) / res_x d_p."""
+        if self.by_fov and name == 'focus_distance':
+            return [('focus_distance', 1.0), ('pixel_size', self.pixel_size / self.focus_distance)]
+        if name == 'fov':
+            half = np.deg2rad(self.fov) / 2
+            return [('pixel_size', float(np.pi / 180 * self.focus_distance / np.cos(half) ** 2 / self.res[0]))]
+        return [(name, 1.0)]
 
     def fill_desc(self, desc):
         self._fill_common(desc)

@@ -29,6 +29,7 @@ class Scene:
         self.integrator = None
         self.shapes = {}
         self.sigma_t_param = None  # traverse()'s 'printing_medium.sigma_t', once traversed
+        self.projector_params = {}  # traverse()'s 'projector.<name>' of a telecentric / lens projector, by name
 
     def emitters(self):
         return [self.projector] if self.projector is not None else []
@@ -146,7 +147,10 @@ def load_dict(scene_dict: dict) -> Scene:
 class SceneParameters(dict):
     """``mi.traverse(scene)`` equivalent for the differentiable projector data and the printing
     medium's extinction ('printing_medium.sigma_t': a 0-dim float32 tensor on the host holding the
-    container's value; ``update`` writes it back, so the next plan is built with it)."""
+    container's value; ``update`` writes it back, so the next plan is built with it).  A telecentric
+    or lens projector adds its calibration, 0-dim float32 host tensors as well: 'projector.distance',
+    'projector.focus_distance', 'projector.aperture_radius' and 'projector.pixel_size', or
+    'projector.fov' for a lens configured by fov."""
 
     def __init__(self, scene: Scene):
         super().__init__()
@@ -158,10 +162,18 @@ class SceneParameters(dict):
             sig = torch.tensor(float(scene.container.sigma_t), dtype=torch.float32)
             dict.__setitem__(self, 'printing_medium.sigma_t', sig)
             scene.sigma_t_param = sig
+        self._calibration = ()
+        if hasattr(p, 'calibration'):
+            cal = p.calibration()
+            self._calibration = tuple(cal)
+            for name, v in cal.items():
+                dict.__setitem__(self, 'projector.' + name, torch.tensor(float(v), dtype=torch.float32))
+            scene.projector_params = {name: self['projector.' + name] for name in cal}
 
     def update(self, values=None):
         if values is not None:
-            for k in ('projector.active_data', 'projector.active_pixels', 'printing_medium.sigma_t'):
+            for k in ('projector.active_data', 'projector.active_pixels', 'printing_medium.sigma_t') + \
+                    tuple('projector.' + name for name in self._calibration):
                 if k in values:
                     dict.__setitem__(self, k, values[k])
         self.scene.projector.set_active(self['projector.active_data'], self['projector.active_pixels'])
@@ -174,6 +186,22 @@ class SceneParameters(dict):
                 raise ValueError("'printing_medium.sigma_t' must be a 0-dim tensor")
             self.scene.container.sigma_t = float(sig.detach().to(torch.float32))
             self.scene.sigma_t_param = sig
+        if self._calibration:
+            cal = {}
+            for name in self._calibration:
+                v = self['projector.' + name]
+                if not isinstance(v, torch.Tensor):
+                    v = torch.tensor(float(v), dtype=torch.float32)
+                    dict.__setitem__(self, 'projector.' + name, v)
+                if v.dim() != 0:
+                    raise ValueError(f"'projector.{name}' must be a 0-dim tensor")
+                cal[name] = v
+            # (a value that still is the projector's own, rounded to float32, leaves it as it is)
+            own = self.scene.projector.calibration()
+            new = {name: float(v.detach().to(torch.float32)) for name, v in cal.items()}
+            self.scene.projector.set_calibration(
+                {name: own[name] if np.float32(own[name]) == np.float32(v) else v for name, v in new.items()})
+            self.scene.projector_params = cal
 
 
 def traverse(scene: Scene) -> SceneParameters:
@@ -183,11 +211,12 @@ def traverse(scene: Scene) -> SceneParameters:
 def render(scene: Scene, params=None, integrator=None, sensor=0, spp: int = 0, spp_grad: int = 0, seed: int = 0,
            seed_grad: Optional[int] = None) -> torch.Tensor:
     """Differentiable render (``mi.render``): gradients flow to projector.active_data, and to
-    traverse(scene)'s 'printing_medium.sigma_t', when they require grad."""
+    traverse(scene)'s 'printing_medium.sigma_t' and 'projector.<calibration>', when they require grad."""
     integrator = integrator or scene.integrator
     x = scene.projector.active_data
     sig = getattr(scene, 'sigma_t_param', None)
-    if (x.requires_grad or (sig is not None and sig.requires_grad)) and torch.is_grad_enabled():
+    cal = any(v.requires_grad for v in getattr(scene, 'projector_params', {}).values())
+    if (x.requires_grad or (sig is not None and sig.requires_grad) or cal) and torch.is_grad_enabled():
         return integrator.render_differentiable(scene, sensor, spp=spp, spp_grad=spp_grad or None, seed=seed,
                                                 seed_grad=seed_grad)
     return integrator.render(scene, sensor, seed=seed, spp=spp)

@@ -443,6 +443,44 @@ int tvam_adjoint_dsigma(tvam_plan* plan, const float* active_data, const float* 
                         double* g_sigma /* device, overwritten */, void* hip_stream);
 int tvam_dsigma_weights(float sigma_t, const float* T0, const float* dt, int64_t n, float* w);
 
+/*
+ * Projector derivatives: d dose / d theta for one parameter theta of a telecentric / lens projector,
+ * in forward and reverse mode.  (Added to ABI v13: no struct or existing
+ * signature changed.)  The derivative is pathwise: the sampler draws, the (ray, sample) -> voxel
+ * bookkeeping and every discrete decision are held fixed, as are the other descriptor fields.  Every
+ * visit's weight e^{-s t_a} - e^{-s t_b} moves with the times t_a, t_b at which the ray crosses the
+ * voxel's faces: s (e^{-s t_b} t_b' - e^{-s t_a} t_a').  Rays that cross the tube's silhouette or its
+ * open ends as theta moves (a visibility change) are not accounted for.
+ *
+ *   param (TVAM_DPROJ_*): 'distance'; 'focus_distance'; 'aperture_radius'; 'pixel_size' =
+ *     pixel_size_x and pixel_size_y moved together (the directional derivative along (1, 1), the ray
+ *     weight ~ p_x p_y included).
+ *   tvam_forward_dprojector: tangent (device, f32, the dose's layout, overwritten) = T[v] =
+ *     d dose[v] / d theta of tvam_forward(active_data).
+ *   tvam_adjoint_dprojector: g[0] (device, f64, overwritten) = sum_v grad_dose[v] T[v].  Per ray a
+ *     gather in f32, the rays summed in f64 in an order that depends on the ray count alone: no float
+ *     atomics, identical calls give identical bits.
+ *   active_data, active_pixels, n_active, spp, seed as in tvam_forward (angle shards, crops, sparse
+ *   sets, clockwise, regular / jittered sampling, sample_time).  Asynchronous on hip_stream.
+ *   Served: telecentric and lens plans of tvam_plan_create behind the index-matched vial, non-scattering
+ *   medium, 'dda' sensor, one-channel film.  Every other plan: TVAM_ERR_UNSUPPORTED, the message
+ *   starting "tvam_forward_dprojector: " / "tvam_adjoint_dprojector: " and naming the cause (a
+ *   collimated projector, a traced 'cylindrical' / 'square' vial, a 'custom' or 'double_cylindrical'
+ *   vial, dielectric occluders, occluders, albedo > 0, the ratio / delta sensors, a surface-aware film,
+ *   a film slab).  A param outside TVAM_DPROJ_* or a null pointer: TVAM_ERR_INVALID.  All checks run
+ *   before any device call; a refusal allocates nothing.
+ */
+#define TVAM_DPROJ_DISTANCE        0
+#define TVAM_DPROJ_FOCUS_DISTANCE  1
+#define TVAM_DPROJ_APERTURE_RADIUS 2
+#define TVAM_DPROJ_PIXEL_SIZE      3
+int tvam_forward_dprojector(tvam_plan* plan, int32_t param, const float* active_data,
+                            const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                            float* tangent /* film, overwritten */, void* hip_stream);
+int tvam_adjoint_dprojector(tvam_plan* plan, int32_t param, const float* active_data, const float* grad_dose,
+                            const uint32_t* active_pixels, uint64_t n_active, uint32_t spp, uint32_t seed,
+                            double* g /* device, overwritten */, void* hip_stream);
+
 /* Update desc.active_base / desc.active_total of a plan (after the active set was
    compacted, e.g. by 'filter_radon', optimize.py:143-163); later calls seed and
    weight their rays with them. */
