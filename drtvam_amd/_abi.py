@@ -190,6 +190,14 @@ class TvamDesc(ctypes.Structure):
         return list(getattr(self, "_inserts", []))
 
     @property
+    def reflected(self) -> bool:
+        """transmission_only = 0 in a scene with a dielectric interface (a 'cylindrical' / 'square' vial or
+        inserts): reflection is sampled there, and engine.Projection creates the plan through
+        tvam_plan_create_reflect, for collimated projectors too (their paths are stochastic and leave the
+        planar kernels).  An index-matched vial without inserts has no interface and is no such scene."""
+        return not self.transmission_only and (self.vial_type in (VIAL_CYLINDRICAL, VIAL_SQUARE) or bool(self.inserts))
+
+    @property
     def traced_vial(self) -> bool:
         return bool(getattr(self, "_traced_vial", False))
 
@@ -219,6 +227,10 @@ EXPORTS = {
                                             ctypes.c_int64, _P, ctypes.c_int32, _P, _P]),
     "tvam_plan_insert_segments": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                                  ctypes.c_int32, _P, _P, _P]),
+    "tvam_plan_create_reflect": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.POINTER(TvamInsert), ctypes.c_int32,
+                                                ctypes.c_int, ctypes.POINTER(_P)]),
+    "tvam_reflect_segments": (ctypes.c_int, [ctypes.POINTER(TvamDesc), ctypes.POINTER(TvamInsert), ctypes.c_int32, _P, _P,
+                                             ctypes.c_int64, _P, ctypes.c_int32, _P, _P]),
     "tvam_plan_segments": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     "tvam_double_segments": (ctypes.c_int, [ctypes.POINTER(TvamDoubleVial), ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_int32, _P, _P, ctypes.c_int64, _P]),
@@ -448,6 +460,30 @@ def insert_segments(desc: TvamDesc, o, d, u=None, max_segments: int = 8):
     check(load_library().tvam_insert_segments(ctypes.byref(desc), arr, len(ins), o.ctypes.data, d.ctypes.data,
                                               o.shape[0], None if u is None else u.ctypes.data, int(max_segments),
                                               segs.ctypes.data, nseg.ctypes.data))
+    return segs, nseg
+
+
+def reflect_segments(desc: TvamDesc, o, d, u, max_segments: int = 8):
+    """insert_segments for a transmission_only = 0 descriptor (tvam_reflect_segments, the reflecting kernels'
+    own walk): after a path's first surface, the iteration's second draw u[:, depth, 1] picks reflection
+    (u <= F) or refraction at every dielectric interface.  u [n, max_depth, 4] is required.  No GPU is touched."""
+    import numpy as np
+    o = np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("reflect_segments: o and d must have the same shape")
+    if u is None:
+        raise ValueError("reflect_segments: u is required (a reflecting walk always draws)")
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    if u.shape != (o.shape[0], int(desc.max_depth), 4):
+        raise ValueError("reflect_segments: u must be [n_rays, max_depth, 4]")
+    ins = desc.inserts
+    arr = insert_array(ins)
+    segs = np.empty((o.shape[0], int(max_segments), 8), np.float32)
+    nseg = np.empty(o.shape[0], np.int32)
+    check(load_library().tvam_reflect_segments(ctypes.byref(desc), arr, len(ins), o.ctypes.data, d.ctypes.data,
+                                               o.shape[0], u.ctypes.data, int(max_segments), segs.ctypes.data,
+                                               nseg.ctypes.data))
     return segs, nseg
 
 

@@ -260,6 +260,7 @@ extern "C" int tvam_forward_slices(tvam_plan* p, const float* active_data, const
                                    uint64_t n_active, uint32_t spp, uint32_t seed, int32_t z_begin, int32_t z_end,
                                    float* dose, void* stream) {
     if (!p) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->refl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_forward_slices: reflected paths (transmission_only = 0) take rays out of their slice (no slice ranges)");
     if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_forward_slices: dielectric occluders take rays out of their slice (no slice ranges)");
     const int ch = fwd_chunk(p), nz = p->k.nz;
     if (ch == 0) return tvam_fail(TVAM_ERR_UNSUPPORTED, "this plan's forward cannot be split into slice ranges");
@@ -296,7 +297,8 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
             const int walk = tvam_plan_walk(p);
             return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream,
                                       tvam_walk_slots(walk) > 0 && tvam_cone_binned(p), walk,
-                                      p->ins   ? "dielectric-occluder forward launch"
+                                      p->refl  ? "reflected-path forward launch"
+                                      : p->ins ? "dielectric-occluder forward launch"
                                       : p->dbl ? "double-vial forward launch"
                                                : "projector-ray forward launch");
         }
@@ -380,6 +382,7 @@ extern "C" int tvam_adjoint_slices(tvam_plan* p, const float* grad_dose, uint64_
                                    int32_t z_end, int32_t row_begin, int32_t row_end, float* grad_active,
                                    void* stream_) {
     if (!p || !grad_dose || !grad_active) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->refl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: reflected paths (transmission_only = 0) take rays out of their slice (no slice ranges)");
     if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: dielectric occluders take rays out of their slice (no slice ranges)");
     if (!p->planar || p->general || p->surface || p->desc.albedo != 0.0f || p->empty)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: planar plans only");
@@ -471,6 +474,7 @@ static int dsigma_refuse(const tvam_plan* p, const char* who) {
     else if (p->k.z0 != 0 || p->k.nz != p->k.res[2]) why = "a film slab is not differentiated (render the whole film)";
     else if (d.sample_time) why = "sample_time is not differentiated";
     else if (p->dbl) why = "a 'double_cylindrical' plan is not differentiated (its second segment starts at the first one's path length)";
+    else if (p->refl) why = "a plan with reflected paths (transmission_only = 0) is not differentiated (its sampled branches do not depend smoothly on the extinction's path)";
     else if (p->ins) why = "a plan with dielectric occluders is not differentiated (its later segments start at the earlier ones' path length)";
     return why ? tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": " + why) : 0;
 }
@@ -528,7 +532,8 @@ static int dproj_check(const tvam_plan* p, int32_t param, const char* who) {
     const tvam_desc& d = p->desc;
     const char* why = nullptr;
     std::string vial;
-    if (p->ins) why = "a plan with dielectric occluders (inserts)";
+    if (p->refl) why = "a plan with reflected paths (transmission_only = 0)";
+    else if (p->ins) why = "a plan with dielectric occluders (inserts)";
     else if (p->dbl) why = "a 'double_cylindrical' vial";
     else if (p->mesh) why = "a 'custom' vial";
     else if (d.vial_type != TVAM_VIAL_INDEX_MATCHED) {
@@ -621,6 +626,7 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
 extern "C" int tvam_plan_segments(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                                   uint32_t seed, float* segs, void* stream_) {
     if (!p || (!segs && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->refl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with reflected paths (transmission_only = 0) has any number of segments per ray (tvam_plan_insert_segments)");
     if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with dielectric occluders has any number of segments per ray (tvam_plan_insert_segments)");
     if (!p->dbl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: 'double_cylindrical' vial plans only");
     if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_segments: segs must be 16-byte aligned");
@@ -631,7 +637,7 @@ extern "C" int tvam_plan_insert_segments(tvam_plan* p, const uint32_t* active_pi
                                          uint32_t seed, int32_t max_segments, float* segs, int32_t* nseg,
                                          void* stream_) {
     if (!p || ((!segs || !nseg) && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (!p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_insert_segments: plans with dielectric occluders only (tvam_plan_create_inserts)");
+    if (!p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_insert_segments: plans with dielectric occluders only (tvam_plan_create_inserts; reflected paths: tvam_plan_create_reflect)");
     if (max_segments <= 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_insert_segments: max_segments must be positive");
     if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_insert_segments: segs must be 16-byte aligned");
     return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_, max_segments, nseg);
@@ -691,6 +697,8 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
                           int32_t max_depth, float* radon, void* stream_) {
     if (!p || !radon || n_target_tris < 0 || (n_target_tris > 0 && !target_tris))
         return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (p->refl)
+        return tvam_fail(TVAM_ERR_UNSUPPORTED, "transmission_only = 0 with filter_radon (the Radon pass's own reflection sampling) is not implemented on the GPU path");
     if (p->ins)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "dielectric occluders with filter_radon are not implemented on the GPU path");
     if (p->mesh)

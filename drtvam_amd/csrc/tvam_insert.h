@@ -28,6 +28,14 @@
 //   the BSDF's next_1d + next_2d are drawn and ignored: four draws per iteration.
 // Every surface counts as depth; the loop runs while depth < max_depth.
 //
+// transmission_only = 0 (tvam_insert_next<REFLECT>, tvam_plan_create_reflect): the same loop with the
+// BSDF's next_1d used.  At depth 0 the transmission is forced as above; at every later dielectric
+// surface s1 <= F reflects (weight 1) and s1 > F refracts with weight eta_ti^2
+// (tvam_dielectric_sample), so total internal reflection reflects instead of ending the path.  The
+// index-matched tube and the black occluders are as above, and so is everything after the BSDF: a
+// reflection off the inner wall from the resin side keeps the medium flag and starts a new segment.
+// Such a walk draws its four numbers in every iteration, whether or not the roulette can act.
+//
 // The walk is resumable: its state is the point, the direction, the attenuation, the depth and the
 // flag, and tvam_insert_next advances it to the next medium segment.  A kernel marches one segment
 // at a time with one copy of its DDA.  All state is scalars: no per-thread array is indexed at run
@@ -66,6 +74,7 @@ TVAM_HD bool tvam_insert_roulette_on(int rr_depth, int max_depth) { return rr_de
 struct TvamInsertHostDraws {
     const float* u;
     TVAM_HD float rr(int depth) const { return u[4 * depth]; }
+    TVAM_HD float s1(int depth) const { return u[4 * depth + 1]; }  // the BSDF's next_1d (a reflecting walk)
     TVAM_HD void bsdf() const {}
 };
 
@@ -75,14 +84,41 @@ struct TvamInsertHostDraws {
 #define TVAM_INS_BLACK 2   // a black occluder
 #define TVAM_INS_INSERT 3  // an insert face
 
+// Mitsuba's dielectric::sample with both lobes enabled and TransportMode::Radiance, in world space:
+// s1 <= F reflects (wo = d - 2 (d . n) n, weight 1), else the refraction of tvam_transmit_world with
+// weight eta_ti^2 (the lobe's probability 1 - F cancels the Fresnel factor).  F = 1 always reflects.
+TVAM_HD float tvam_dielectric_sample(float nx, float ny, float nz, float dx, float dy, float dz, float eta, float s1,
+                                     float& wx, float& wy, float& wz) {
+    const float cos_i = -(dx * nx + dy * ny + dz * nz);
+    float cos_t, eta_ti;
+    const float r = tvam_fresnel(cos_i, eta, cos_t, eta_ti);
+    if (s1 <= r) {
+        const float c = 2.0f * cos_i;
+        wx = dx + c * nx;
+        wy = dy + c * ny;
+        wz = dz + c * nz;
+        return 1.0f;
+    }
+    const float c = eta_ti * cos_i + cos_t;
+    wx = eta_ti * dx + c * nx;
+    wy = eta_ti * dy + c * ny;
+    wz = eta_ti * dz + c * nz;
+    return eta_ti * eta_ti;
+}
+
 // The walk to its next medium segment (o2, d2, [0, maxt]) of weight `weight` (the attenuation the
 // segment starts with); false: the path has ended.  rr: Russian roulette is drawn (draws.rr(depth)
 // per iteration, draws.bsdf() after a valid hit).  `iter` (host checks): the loop iteration of the
 // deposit.
-template <typename DRAWS>
+//
+// REFLECT (tvam_plan_create_reflect, transmission_only = 0): after the path's first surface every
+// dielectric interface samples reflection against refraction with draws.s1(depth), the BSDF's
+// next_1d (tvam_dielectric_sample); total internal reflection reflects instead of ending the path.
+// Such a walk always draws (rr = true).  MESHES = false: a scene without inserts, no hierarchy read.
+template <bool REFLECT = false, bool MESHES = true, typename DRAWS>
 TVAM_HD bool tvam_insert_next(const TvamConsts& k, const TvamInsertScene& sc, bool rr, DRAWS& draws, TvamInsertWalk& w,
                               float o2[3], float d2[3], float& maxt, float& weight, int* iter = nullptr) {
-    const bool brute = sc.mesh.n_tris <= TVAM_MESH_BRUTE_MAX;
+    const bool brute = MESHES && sc.mesh.n_tris <= TVAM_MESH_BRUTE_MAX;
     while (w.depth < k.max_depth) {
         if (rr) {  // volume.py:181-186
             const float q = fminf(0.99f, w.att);
@@ -124,12 +160,16 @@ TVAM_HD bool tvam_insert_next(const TvamConsts& k, const TvamInsertScene& sc, bo
             const float tb = tvam_occ_hit(k, w.px, w.py, w.pz, w.vx, w.vy, w.vz);
             if (tb < t) t = tb, kind = TVAM_INS_BLACK;
         }
-        int slot;
-        const float tm = brute ? tvam_mesh_closest_brute(sc.mesh, TVAM_MESH_BOTH, w.px, w.py, w.pz, w.vx, w.vy, w.vz, slot)
-                               : tvam_mesh_closest(sc.mesh, TVAM_MESH_BOTH, w.px, w.py, w.pz, w.vx, w.vy, w.vz, slot);
-        if (tm < t) t = tm, kind = TVAM_INS_INSERT;
+        int slot = 0;
+        if constexpr (MESHES) {
+            const float tm = brute ? tvam_mesh_closest_brute(sc.mesh, TVAM_MESH_BOTH, w.px, w.py, w.pz, w.vx, w.vy, w.vz, slot)
+                                   : tvam_mesh_closest(sc.mesh, TVAM_MESH_BOTH, w.px, w.py, w.pz, w.vx, w.vy, w.vz, slot);
+            if (tm < t) t = tm, kind = TVAM_INS_INSERT;
+        }
         if (!(t < TVAM_INF)) break;
-        if (rr) draws.bsdf();
+        float s1 = 0.0f;
+        if constexpr (REFLECT) s1 = draws.s1(w.depth);
+        else if (rr) draws.bsdf();
         const bool seg = w.in_medium;
         if (seg) {
             o2[0] = w.px, o2[1] = w.py, o2[2] = w.pz;
@@ -151,8 +191,10 @@ TVAM_HD bool tvam_insert_next(const TvamConsts& k, const TvamInsertScene& sc, bo
             nx = hx / rp, ny = hy / rp, nz = 0.0f;
         }
         float wx = w.vx, wy = w.vy, wz = w.vz, tw = 1.0f;
-        if (k.vial_type != 0 || kind == TVAM_INS_INSERT)
-            tw = tvam_transmit_world(nx, ny, nz, w.vx, w.vy, w.vz, eta, wx, wy, wz);
+        if (k.vial_type != 0 || kind == TVAM_INS_INSERT) {
+            if (REFLECT && w.depth > 0) tw = tvam_dielectric_sample(nx, ny, nz, w.vx, w.vy, w.vz, eta, s1, wx, wy, wz);
+            else tw = tvam_transmit_world(nx, ny, nz, w.vx, w.vy, w.vz, eta, wx, wy, wz);
+        }
         if (!(tw > 0.0f)) {
             w.depth = k.max_depth;
             return seg;

@@ -305,7 +305,15 @@ hipError_t tvam_launch_general_paths(int mode, const TvamConsts& k, const TvamTi
 //   TVAM_WALK_DOUBLE  'double_cylindrical': at most two, in front of the inner vial and behind it
 //   TVAM_WALK_INSERT  dielectric occluders: any number (k.mesh: the hierarchy over all inserts;
 //                     aux: device [n_tris] eta by caller-order triangle, null for the other walks)
-enum TvamWalk { TVAM_WALK_NONE = -1, TVAM_WALK_ONE = 0, TVAM_WALK_DOUBLE = 1, TVAM_WALK_INSERT = 2 };
+//   TVAM_WALK_REFLECT transmission_only = 0: the insert walk with reflection sampled at every
+//                     dielectric interface after the first; k.mesh.n_tris may be 0 (no inserts)
+enum TvamWalk {
+    TVAM_WALK_NONE = -1,
+    TVAM_WALK_ONE = 0,
+    TVAM_WALK_DOUBLE = 1,
+    TVAM_WALK_INSERT = 2,
+    TVAM_WALK_REFLECT = 3
+};
 // record slots per path of the binned forward (0: unbounded, no binned forward)
 inline int tvam_walk_slots(int walk) { return walk == TVAM_WALK_ONE ? 1 : (walk == TVAM_WALK_DOUBLE ? 2 : 0); }
 // Per-ray kernels (forward: global atomics, `out` zeroed by the caller; adjoint: gathers, `out`

@@ -46,6 +46,7 @@ struct tvam_plan {
     bool dbl = false;        // 'double_cylindrical' vial: four tubes traced per ray, two segments (tvam_double.h); implies cone
     bool traced = false;     // 'cylindrical' / 'square' vial traced per ray in 3-D (tvam_plan_create_traced, tvam_glass.h); implies cone
     bool ins = false;        // dielectric occluders walked per ray (tvam_plan_create_inserts, tvam_insert.h); implies cone
+    bool refl = false;       // transmission_only = 0 (tvam_plan_create_reflect): the insert walk with sampled reflections; implies ins
     TvamDevBuf<float> ins_eta;      // ... eta of each insert triangle, caller order (the hierarchy: mesh_*)
     TvamDevBuf<float4> mesh_nodes;  // 'custom' vial: the hierarchy over both meshes (TvamMesh)
     TvamDevBuf<float> mesh_tris;
@@ -138,7 +139,7 @@ inline bool tvam_cone_binned(const tvam_plan* p) {
 
 // the walk of a 3-D ray plan (p->cone; tvam_ray3d.h)
 inline int tvam_plan_walk(const tvam_plan* p) {
-    return p->ins ? TVAM_WALK_INSERT : (p->dbl ? TVAM_WALK_DOUBLE : TVAM_WALK_ONE);
+    return p->refl ? TVAM_WALK_REFLECT : p->ins ? TVAM_WALK_INSERT : (p->dbl ? TVAM_WALK_DOUBLE : TVAM_WALK_ONE);
 }
 
 // one medium segment as the host segment dumpers write it: o2[3], maxt, d2[3], att

@@ -85,7 +85,9 @@ extern "C" void tvam_plan_destroy(tvam_plan* p) {
 // traced: the descriptor of tvam_plan_create_traced (a 'cylindrical' / 'square' vial on the 3-D
 // per-ray path, any projector kind)
 // inserts: the descriptor of tvam_plan_create_inserts (dielectric occluders walked per ray)
-static int validate(const tvam_desc& d, bool traced = false, bool inserts = false) {
+// reflect: with inserts, the descriptor of tvam_plan_create_reflect (transmission_only = 0: the same
+// walk with reflection sampled at the dielectric interfaces)
+static int validate(const tvam_desc& d, bool traced = false, bool inserts = false, bool reflect = false) {
     if (d.abi_version != TVAM_ABI_VERSION) return tvam_fail(TVAM_ERR_INVALID, "tvam_desc.abi_version mismatch");
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED && d.projector_type != TVAM_PROJECTOR_TELECENTRIC &&
         d.projector_type != TVAM_PROJECTOR_LENS)
@@ -98,8 +100,11 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         // limits these are (Russian roulette is honoured: no limit on rr_depth)
         auto no = [&](const char* what) {
             return tvam_fail(TVAM_ERR_UNSUPPORTED,
-                             std::string("dielectric occluders with ") + what + " are not implemented on the GPU path");
+                             reflect ? std::string("transmission_only = 0 with ") + what + " is not implemented on the GPU path"
+                                     : std::string("dielectric occluders with ") + what + " are not implemented on the GPU path");
         };
+        if (reflect && d.transmission_only)
+            return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_reflect: transmission_only = 1 belongs to tvam_plan_create and its siblings");
         if (d.vial_type == TVAM_VIAL_CUSTOM) return no("a 'custom' vial");
         if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) return no("a 'double_cylindrical' vial");
         if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
@@ -112,7 +117,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
         if (d.film_channels == 2) return no("a surface-aware film");
         if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
-        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the interfaces)");
+        if (!reflect && !d.transmission_only) return no("transmission_only = 0 (reflected paths at the interfaces)");
     } else if (d.vial_type == TVAM_VIAL_CUSTOM) {
         // mesh vial (tvam_plan_create_mesh): every ray is traced in 3-D through the interfaces and
         // runs the per-ray kernels of tvam_ray3d.hip, whose limits these are
@@ -225,7 +230,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
     // transmission_only = False lets the reference sample reflection as well as refraction at every
     // dielectric interface after the first (volume.py:235-243, radon.py:87-95); the kernels only
     // refract.  An index-matched vial has no such interface.
-    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !d.transmission_only)
+    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !d.transmission_only && !reflect)
         return tvam_fail(TVAM_ERR_UNSUPPORTED,
                          std::string("transmission_only = 0 behind a ") +
                              (d.vial_type == TVAM_VIAL_SQUARE ? "'square'" : "'cylindrical'") +
@@ -1321,7 +1326,7 @@ static int upload_vial_meshes(tvam_plan* p, const float* outer, int32_t n_outer,
 
 static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
                        const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced = false,
-                       const tvam_insert* inserts = nullptr, int32_t n_inserts = 0);
+                       const tvam_insert* inserts = nullptr, int32_t n_inserts = 0, bool reflect = false);
 // tvam_double.hip
 int tvam_double_validate(const tvam_double_vial* v, float medium_ior);
 TvamDouble tvam_double_consts(const tvam_double_vial& v, float medium_ior);
@@ -1383,6 +1388,71 @@ extern "C" int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* in
             if (s < max_segments) {
                 seg_row(row + 8 * s, o2, d2, maxt, att);
             }
+            ++s;
+        }
+        nseg[i] = s;
+    }
+    return 0;
+}
+
+// transmission_only = 0: the walk of tvam_plan_create_inserts with reflection sampled against
+// refraction at every dielectric interface after a path's first (tvam_insert_next<true>).  A glass
+// vial needs no insert; the index-matched tube has no interface of its own and needs one.
+static int reflect_validate(const tvam_desc& d, const tvam_insert* inserts, int32_t n_inserts) {
+    int rc = validate(d, false, true, true);
+    if (rc) return rc;
+    if (n_inserts < 0 || (n_inserts > 0 && !inserts))
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_reflect: inserts is null");
+    if (n_inserts == 0 && d.vial_type == TVAM_VIAL_INDEX_MATCHED)
+        return tvam_fail(TVAM_ERR_INVALID, "transmission_only = 0 behind an 'index_matched' vial without inserts has no dielectric interface: create the plan with tvam_plan_create");
+    return n_inserts > 0 ? tvam_inserts_validate(make_consts(d, 0, 0), inserts, n_inserts) : 0;
+}
+
+extern "C" int tvam_plan_create_reflect(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                        int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    int rc = reflect_validate(*desc, inserts, n_inserts);
+    if (rc) return rc;
+    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out, false, inserts, n_inserts, true);
+}
+
+// The host walk of such a plan, ray by ray: no device call.  u [n_rays][max_depth][4] is required:
+// a reflecting walk always draws.
+extern "C" int tvam_reflect_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                     const float* o, const float* d, int64_t n_rays, const float* u,
+                                     int32_t max_segments, float* segs, int32_t* nseg) {
+    if (!desc || n_rays < 0 || max_segments < 0 || (n_rays > 0 && (!o || !d || !nseg || (max_segments > 0 && !segs))))
+        return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (n_rays > 0 && !u) return tvam_fail(TVAM_ERR_INVALID, "tvam_reflect_segments: u is required (a reflecting walk always draws)");
+    int rc = reflect_validate(*desc, inserts, n_inserts);
+    if (rc) return rc;
+    TvamConsts k = make_consts(*desc, 0, 0);
+    if (desc->n_occluder_tris > 0) {
+        k.occ = desc->occluder_tris;
+        occ_bounds(k, desc->occluder_tris, desc->n_occluder_tris);
+    }
+    std::vector<float> tris, tri_eta;
+    TvamMeshHost h;
+    TvamInsertScene sc{};
+    if (n_inserts > 0) {
+        tvam_inserts_flatten(inserts, n_inserts, tris, tri_eta);
+        tvam_mesh_build(tris.data(), (int32_t)tri_eta.size(), h);
+        sc.mesh.nodes = h.nodes.data(), sc.mesh.tris = h.tris.data(), sc.mesh.ids = h.ids.data();
+        sc.mesh.n_nodes = (int32_t)(h.nodes.size() / 2), sc.mesh.n_tris = (int32_t)tri_eta.size(), sc.mesh.n_inner = 0;
+        sc.tri_eta = tri_eta.data();
+    }
+    for (int64_t i = 0; i < n_rays; ++i) {
+        TvamInsertWalk w;
+        tvam_insert_start(w, o + 3 * i, d + 3 * i);
+        TvamInsertHostDraws dr{u + 4 * (size_t)k.max_depth * (size_t)i};
+        float* row = segs + 8 * (size_t)max_segments * (size_t)i;
+        if (max_segments > 0) std::fill(row, row + 8 * (size_t)max_segments, 0.0f);
+        int32_t s = 0;
+        float o2[3], d2[3], maxt, att;
+        while (n_inserts > 0 ? tvam_insert_next<true, true>(k, sc, true, dr, w, o2, d2, maxt, att)
+                             : tvam_insert_next<true, false>(k, sc, true, dr, w, o2, d2, maxt, att)) {
+            if (s < max_segments) seg_row(row + 8 * s, o2, d2, maxt, att);
             ++s;
         }
         nseg[i] = s;
@@ -1453,13 +1523,13 @@ extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_t
 
 static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_outer, const float* inner,
                        int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced,
-                       const tvam_insert* inserts, int32_t n_inserts) {
+                       const tvam_insert* inserts, int32_t n_inserts, bool reflect) {
     tvam_desc d = d_in;
     if (dbl) {  // the host tables (tiles, slots) are sized by the medium's tube and the outermost one
         d.vial_r = dbl->r_int_outer;
         d.vial_r_ext = dbl->r_ext_outer;
     }
-    int rc = validate(d, traced, inserts != nullptr);
+    int rc = validate(d, traced, inserts != nullptr || reflect, reflect);
     if (rc) return rc;
     int a0 = d.angle_begin, a1 = d.angle_end < 0 ? d.n_patterns : d.angle_end;
     if (a0 < 0 || a1 > d.n_patterns || a0 > a1) return tvam_fail(TVAM_ERR_INVALID, "invalid angle shard");
@@ -1486,7 +1556,8 @@ static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_oute
         p->empty = d.max_depth < 3;  // the first deposit is at loop iteration 2
         p->k.dbl = tvam_double_consts(*dbl, d.medium_ior);
     }
-    p->ins = inserts != nullptr;
+    p->ins = inserts != nullptr || reflect;  // (a reflecting plan runs the insert walk, with or without inserts)
+    p->refl = reflect;
     if (p->ins) {  // a glass vial under the inserts is a traced one (the planar tables are not this path's)
         traced = p->cyl;
         p->empty = d.max_depth < (p->cyl ? 3 : 2);
@@ -1497,7 +1568,7 @@ static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_oute
     p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
     if ((rc = upload_meshes(p.get())) || (rc = tile_geometry(p.get()))) return rc;
     if (p->mesh && (rc = upload_vial_meshes(p.get(), outer, n_outer, inner, n_inner))) return rc;
-    if (p->ins && (rc = upload_inserts(p.get(), inserts, n_inserts))) return rc;
+    if (p->ins && n_inserts > 0 && (rc = upload_inserts(p.get(), inserts, n_inserts))) return rc;
 
     std::vector<float2> cs;
     std::vector<float4> ang;

@@ -73,6 +73,13 @@ struct InsDraws {
         (void)rng.next_float();
         (void)rng.next_float();
     }
+    // (a reflecting walk uses the first of the BSDF's three: next_1d)
+    __device__ __forceinline__ float s1(int) {
+        const float s = rng.next_float();
+        (void)rng.next_float();
+        (void)rng.next_float();
+        return s;
+    }
 };
 
 // Dielectric occluders: the resumable walk of tvam_insert.h, which goes on drawing from the ray's
@@ -97,6 +104,31 @@ struct WalkInsert {
     }
     __device__ __forceinline__ bool next(const TvamConsts& k, ConeRay& r, State& st) const {
         return tvam_insert_next(k, sc, rr, st.dr, st.w, r.o2, r.d2, r.maxt, r.att);
+    }
+};
+
+// transmission_only = 0 (tvam_plan_create_reflect): the same walk with reflection sampled against
+// refraction at every dielectric interface after the first (tvam_insert_next<true>).  It always
+// draws its four numbers per surface iteration.  MESH: CN_MESH_LDS, CN_MESH_GLOBAL, or CN_NO_MESH
+// for a plan without inserts (no hierarchy is read); aux: tri_eta.
+template <int MESH>
+struct WalkReflect {
+    static constexpr int SLOTS = 0;
+    TvamInsertScene sc;
+    struct State {
+        InsDraws dr;
+        TvamInsertWalk w;
+    };
+    __device__ __forceinline__ WalkReflect(const TvamConsts& k, const float* tri_eta)
+        : sc{cn_mesh_view<MESH>(k, r3_mesh_lds), tri_eta} {}
+    __device__ __forceinline__ void start(const TvamConsts& k, const TvamTiles& tp, const int32_t* idxmap,
+                                          const TvamPathIndex& ix, ConeRay& r, State& st) const {
+        (void)cn_ray_at<CN_NO_MESH, true>(k, tp, ix.al, ix.colc, ix.rowc,
+                                          tvam_stream(k, idxmap, ix.local, tp.spp, ix.smp), r, st.dr.rng);
+        tvam_insert_start(st.w, r.o, r.d);
+    }
+    __device__ __forceinline__ bool next(const TvamConsts& k, ConeRay& r, State& st) const {
+        return tvam_insert_next<true, MESH != CN_NO_MESH>(k, sc, true, st.dr, st.w, r.o2, r.d2, r.maxt, r.att);
     }
 };
 

@@ -1,6 +1,6 @@
 // 3-D ray plans: projector rays with a finite etendue (telecentric and lens projectors,
 // projector.py:199-296) and vials traced per ray in 3-D ('custom' meshes, traced 'cylindrical' /
-// 'square' glass, 'double_cylindrical', dielectric occluders).  Such a ray leaves its z-slice, so
+// 'square' glass, 'double_cylindrical', dielectric occluders, reflected paths).  Such a ray leaves its z-slice, so
 // none of the planar / tile kernels (d.z = 0) applies.  The pieces are the scattered segments' own
 // (tvam_seg3d.h, tvam_bricks.h: the 3-D DDA and the brick bins), the ray generation of
 // tvam_cone_ray.h and, for what tells the plans apart, the walk policies of tvam_ray3d.h.
@@ -168,6 +168,10 @@ void r3_dispatch(int walk, const TvamConsts& k, F&& f) {
     if (walk == TVAM_WALK_INSERT) {
         if (k.mesh.lds_bytes > 0) f(R3Walk<WalkInsert<CN_MESH_LDS>>{}, cn_mesh_lds_bytes(k.mesh));
         else f(R3Walk<WalkInsert<CN_MESH_GLOBAL>>{}, (size_t)0);
+    } else if (walk == TVAM_WALK_REFLECT) {
+        if (k.mesh.n_tris <= 0) f(R3Walk<WalkReflect<CN_NO_MESH>>{}, (size_t)0);
+        else if (k.mesh.lds_bytes > 0) f(R3Walk<WalkReflect<CN_MESH_LDS>>{}, cn_mesh_lds_bytes(k.mesh));
+        else f(R3Walk<WalkReflect<CN_MESH_GLOBAL>>{}, (size_t)0);
     } else if (walk == TVAM_WALK_DOUBLE) {
         f(R3Walk<WalkDouble>{}, (size_t)0);
     } else {

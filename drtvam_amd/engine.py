@@ -59,7 +59,11 @@ class Projection:
             self.device = torch.device("cuda", torch.cuda.current_device())
         plan = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            if self.desc.inserts:  # dielectric occluders travel beside the struct (set_inserts)
+            if self.desc.reflected:  # transmission_only = 0: reflections sampled at the glass and the inserts
+                ins = self.desc.inserts
+                _abi.check(self.lib.tvam_plan_create_reflect(ctypes.byref(self.desc), _abi.insert_array(ins), len(ins),
+                                                             self.device.index, ctypes.byref(plan)))
+            elif self.desc.inserts:  # dielectric occluders travel beside the struct (set_inserts)
                 ins = self.desc.inserts
                 _abi.check(self.lib.tvam_plan_create_inserts(ctypes.byref(self.desc), _abi.insert_array(ins), len(ins),
                                                              self.device.index, ctypes.byref(plan)))
@@ -364,7 +368,9 @@ class Projection:
         """Every medium segment of a call's rays through a resin with dielectric occluders
         (tvam_plan_insert_segments): (segs [n_active * spp, max_segments, 8] float32 in sampler-stream order:
         o2[0:3], maxt [3], d2[4:7], weight [7] (the whole per-ray weight times the attenuation the segment
-        starts with), zeros past a ray's segments; nseg [n_active * spp] int32, the segments each ray has)."""
+        starts with), zeros past a ray's segments; nseg [n_active * spp] int32, the segments each ray has).
+        A transmission_only = 0 plan (tvam_plan_create_reflect) is served too: its reflected segments are among
+        them, in path order."""
         if active_pixels is not None:
             self._check_pixels(active_pixels)
             n_active = int(active_pixels.numel())

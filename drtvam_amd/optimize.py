@@ -538,8 +538,11 @@ class TvamProblem(ShardedLoop):
         double = int(full_desc.vial_type) == 4  # _abi.VIAL_DOUBLE_CYLINDRICAL: nested tubes, 3-D per-ray path
         traced = full_desc.traced_vial  # glass tube / cuvette traced per ray (tvam_plan_create_traced): 3-D per-ray path
         inserts = bool(full_desc.inserts)  # dielectric occluders walked per ray (tvam_plan_create_inserts): 3-D per-ray path
+        # transmission_only = false behind a glass vial or with inserts: reflections sampled per ray
+        # (tvam_plan_create_reflect), the 3-D per-ray path for collimated configs too
+        reflected = bool(full_desc.reflected)
         if 'flags' not in config and (full_desc.albedo != 0.0 or int(full_desc.projector_type) != 0 or custom or double
-                                      or traced or inserts):
+                                      or traced or inserts or reflected):
             # every path marched, as the reference marches every active pixel (projector.py:66-70,
             # common.py:81-82): a scattering scene's paths (and a telecentric / lens projector's
             # binned first segments) then do not depend on the pattern, and
@@ -575,7 +578,13 @@ class TvamProblem(ShardedLoop):
                              "and take them out of their slice (use shard 'angle')")
         if inserts and config.get('filter_radon', False) and filter_pixels:
             raise NotImplementedError("filter_radon with dielectric occluders is not implemented on the GPU path")
-        cone = int(full_desc.projector_type) != 0 or custom or double or traced or inserts
+        if reflected and shard == 'slab':
+            raise ValueError("z-slab sharding needs planar rays: with transmission_only = false the paths reflect at the "
+                             "glass and the inserts and leave their slice (use shard 'angle')")
+        if reflected and config.get('filter_radon', False) and filter_pixels:
+            raise NotImplementedError("filter_radon with transmission_only = false (the Radon pass's own reflection "
+                                      "sampling) is not implemented on the GPU path")
+        cone = int(full_desc.projector_type) != 0 or custom or double or traced or inserts or reflected
         if cone and shard == 'slab':
             raise ValueError("z-slab sharding needs planar rays: the 'telecentric' and 'lens' projectors' rays "
                              "leave their slice (use shard 'angle')")

@@ -360,10 +360,46 @@ int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* inserts, int3
  * The same on the device for a call's rays: segs [n_active * spp][max_segments][8] floats (16-byte
  * aligned) and nseg [n_active * spp] in sampler-stream order as tvam_plan_segments defines it, the
  * weight as there (the whole per-ray weight times the attenuation the segment starts with).
- * TVAM_ERR_UNSUPPORTED on a plan that tvam_plan_create_inserts did not make.
+ * TVAM_ERR_UNSUPPORTED on a plan that neither tvam_plan_create_inserts nor tvam_plan_create_reflect
+ * made.
  */
 int tvam_plan_insert_segments(tvam_plan* plan, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                               uint32_t seed, int32_t max_segments, float* segs, int32_t* nseg, void* hip_stream);
+
+/*
+ * Reflected paths: a plan for transmission_only = 0 (common.py:19; every other entry refuses that
+ * value behind a refracting container).  The walk is tvam_plan_create_inserts' with the BSDF's
+ * first draw used: at a path's first surface the transmission is forced as there, weight
+ * (1 - F) eta_ti^2; at every later dielectric surface (the vial's outer and inner glass, an insert
+ * face) the iteration's second draw s1 is compared with the Fresnel reflectance F: s1 <= F reflects
+ * (wo = d - 2 (d . n) n, weight 1), otherwise the ray refracts with weight eta_ti^2.  Total internal
+ * reflection (F = 1) therefore reflects and no longer ends the path.  The index-matched tube still
+ * passes the ray on and a black occluder still ends it.  After either branch: e^{-sigma_t t} after a
+ * medium segment, the spawn offset on the side of wo, the medium flag (container's medium boundary
+ * and n . wo < 0, or insert face and n . wo > 0: a reflection off the inner wall from the resin
+ * stays in the resin and starts a new segment), ++depth.  Such a walk draws its four numbers in
+ * every iteration, whether or not Russian roulette can act.
+ * Accepted: 'cylindrical' and 'square' vials with n_inserts >= 0, 'index_matched' with
+ * n_inserts >= 1, the three projectors, black occluders, crop, clockwise, regular and jittered
+ * sampling, sample_time, dense and sparse sets, angle shards, any max_depth / rr_depth.
+ * TVAM_ERR_INVALID: transmission_only = 1 (that mode is the other entries'), an index-matched vial
+ * without inserts, and tvam_plan_create_inserts' mesh checks.  TVAM_ERR_UNSUPPORTED, as
+ * "transmission_only = 0 with <what>": albedo > 0, the ratio / delta sensors, a surface-aware film,
+ * film slabs, a 'custom' or 'double_cylindrical' vial.  All before any device call.  tvam_forward,
+ * tvam_adjoint, tvam_corner, tvam_count_visits, tvam_plan_rays and tvam_plan_insert_segments serve
+ * such a plan; tvam_radon, the dsigma and dprojector entries, the slice entries and
+ * tvam_plan_segments refuse it by name.
+ */
+int tvam_plan_create_reflect(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts, int device,
+                             tvam_plan** plan);
+
+/*
+ * That walk on the host, as tvam_insert_segments; u ([n_rays][max_depth][4]: roulette, s1, and the
+ * two of s2, unused) is required.
+ */
+int tvam_reflect_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts, const float* o,
+                          const float* d, int64_t n_rays, const float* u, int32_t max_segments, float* segs,
+                          int32_t* nseg);
 
 /*
  * Forward projection (primal render).  Writes the whole film
