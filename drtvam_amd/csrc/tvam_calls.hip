@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstring>
 
+using K = TvamPlanKind;
+
 // tvam_scatter_binned found brick walks that disagree with the record writer's counts
 static int bin_mismatch_fail(tvam_plan* p) {
     uint32_t bad = 0;
@@ -256,12 +258,21 @@ extern "C" int tvam_forward(tvam_plan* p, const float* active_data, const uint32
     return forward_impl(p, active_data, active_pixels, n_active, spp, seed, dose, stream_, 0, -1);
 }
 
+// What tvam_forward_slices and tvam_adjoint_slices (`who`) refuse by name (the other 3-D ray kinds: the entries' own checks)
+static int slices_refuse(const tvam_plan* p, const char* who) {
+    switch (p->kind) {
+    case K::Reflect: return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": reflected paths (transmission_only = 0) take rays out of their slice (no slice ranges)");
+    case K::Inserts: return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": dielectric occluders take rays out of their slice (no slice ranges)");
+    case K::Plain: case K::Cone: case K::Traced: case K::Mesh: case K::Double: break;
+    }
+    return 0;
+}
+
 extern "C" int tvam_forward_slices(tvam_plan* p, const float* active_data, const uint32_t* active_pixels,
                                    uint64_t n_active, uint32_t spp, uint32_t seed, int32_t z_begin, int32_t z_end,
                                    float* dose, void* stream) {
     if (!p) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (p->refl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_forward_slices: reflected paths (transmission_only = 0) take rays out of their slice (no slice ranges)");
-    if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_forward_slices: dielectric occluders take rays out of their slice (no slice ranges)");
+    if (const int rc = slices_refuse(p, "tvam_forward_slices")) return rc;
     const int ch = fwd_chunk(p), nz = p->k.nz;
     if (ch == 0) return tvam_fail(TVAM_ERR_UNSUPPORTED, "this plan's forward cannot be split into slice ranges");
     if (z_begin < 0 || z_end > nz || z_begin >= z_end || z_begin % ch != 0 || (z_end % ch != 0 && z_end != nz))
@@ -293,14 +304,14 @@ static int forward_impl(tvam_plan* p, const float* active_data, const uint32_t* 
     if ((rc = bind_active(p, kc, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
     if (p->general) {
         TvamTiles t = call_tiles(p, spp, seed);
-        if (p->cone) {  // a record slot per possible segment; any number of them: the per-ray atomics alone
+        if (tvam_kind_ray3d(p->kind)) {  // a record slot per possible segment; any number of them: the per-ray atomics alone
             const int walk = tvam_plan_walk(p);
             return scattered_segments(TVAM_MODE_FWD, p, kc, t, pat, idxmap, nullptr, dose, stream,
                                       tvam_walk_slots(walk) > 0 && tvam_cone_binned(p), walk,
-                                      p->refl  ? "reflected-path forward launch"
-                                      : p->ins ? "dielectric-occluder forward launch"
-                                      : p->dbl ? "double-vial forward launch"
-                                               : "projector-ray forward launch");
+                                      p->kind == K::Reflect   ? "reflected-path forward launch"
+                                      : p->kind == K::Inserts ? "dielectric-occluder forward launch"
+                                      : p->kind == K::Double  ? "double-vial forward launch"
+                                                                         : "projector-ray forward launch");
         }
         e = tvam_launch_general_paths(TVAM_MODE_FWD, kc, t, pat, idxmap, nullptr, dose, nullptr, stream);
         return e == hipSuccess ? 0 : tvam_hip_fail(e, "path forward launch");
@@ -382,8 +393,7 @@ extern "C" int tvam_adjoint_slices(tvam_plan* p, const float* grad_dose, uint64_
                                    int32_t z_end, int32_t row_begin, int32_t row_end, float* grad_active,
                                    void* stream_) {
     if (!p || !grad_dose || !grad_active) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (p->refl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: reflected paths (transmission_only = 0) take rays out of their slice (no slice ranges)");
-    if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: dielectric occluders take rays out of their slice (no slice ranges)");
+    if (const int rc = slices_refuse(p, "tvam_adjoint_slices")) return rc;
     if (!p->planar || p->general || p->surface || p->desc.albedo != 0.0f || p->empty)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_adjoint_slices: planar plans only");
     hipStream_t stream = (hipStream_t)stream_;
@@ -431,8 +441,9 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
     if (p->general) {
         if (p->empty) return 0;
         TvamTiles t = call_tiles(p, spp, seed);
-        e = p->cone ? launch_ray3d(TVAM_MODE_ADJ, p, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
-                    : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
+        e = tvam_kind_ray3d(p->kind)
+                ? launch_ray3d(TVAM_MODE_ADJ, p, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream)
+                : tvam_launch_general_paths(TVAM_MODE_ADJ, k, t, nullptr, idxmap, grad_dose, grad_active, nullptr, stream);
         return e == hipSuccess ? 0 : tvam_hip_fail(e, "path adjoint launch");
     }
     if (p->surface) {
@@ -464,7 +475,7 @@ extern "C" int tvam_adjoint(tvam_plan* p, const float* grad_dose, const uint32_t
 }
 
 // Extinction derivatives (tvam_dsigma.hip).  What both entries refuse, from the descriptor and the
-// plan's flags alone: no device call, nothing allocated.
+// plan's kind alone: no device call, nothing allocated.
 static int dsigma_refuse(const tvam_plan* p, const char* who) {
     const tvam_desc& d = p->desc;
     const char* why = nullptr;
@@ -473,9 +484,13 @@ static int dsigma_refuse(const tvam_plan* p, const char* who) {
     else if (p->surface) why = "a surface-aware (two-channel) film is not differentiated";
     else if (p->k.z0 != 0 || p->k.nz != p->k.res[2]) why = "a film slab is not differentiated (render the whole film)";
     else if (d.sample_time) why = "sample_time is not differentiated";
-    else if (p->dbl) why = "a 'double_cylindrical' plan is not differentiated (its second segment starts at the first one's path length)";
-    else if (p->refl) why = "a plan with reflected paths (transmission_only = 0) is not differentiated (its sampled branches do not depend smoothly on the extinction's path)";
-    else if (p->ins) why = "a plan with dielectric occluders is not differentiated (its later segments start at the earlier ones' path length)";
+    else
+        switch (p->kind) {
+        case K::Double: why = "a 'double_cylindrical' plan is not differentiated (its second segment starts at the first one's path length)"; break;
+        case K::Reflect: why = "a plan with reflected paths (transmission_only = 0) is not differentiated (its sampled branches do not depend smoothly on the extinction's path)"; break;
+        case K::Inserts: why = "a plan with dielectric occluders is not differentiated (its later segments start at the earlier ones' path length)"; break;
+        case K::Plain: case K::Cone: case K::Traced: case K::Mesh: break;  // one medium segment per ray: differentiated
+        }
     return why ? tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": " + why) : 0;
 }
 
@@ -494,7 +509,7 @@ extern "C" int tvam_forward_dsigma(tvam_plan* p, const float* active_data, const
     const float* pat = active_data;
     const int32_t* idxmap = nullptr;
     if ((rc = bind_active(p, k, active_data, active_pixels, n_active, stream, &pat, &idxmap))) return rc;
-    e = tvam_launch_dsigma(TVAM_MODE_FWD, p->cone, k, call_tiles(p, spp, seed), pat, idxmap, nullptr, tangent, nullptr,
+    e = tvam_launch_dsigma(TVAM_MODE_FWD, tvam_kind_ray3d(p->kind), k, call_tiles(p, spp, seed), pat, idxmap, nullptr, tangent, nullptr,
                            nullptr, stream);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "extinction tangent launch");
 }
@@ -521,26 +536,31 @@ extern "C" int tvam_adjoint_dsigma(tvam_plan* p, const float* active_data, const
     // (the grid, and with it the order of the sum, depends on the ray count alone)
     if ((e = p->dsig_part.grow(tvam_dsigma_grid((int64_t)t.n_shard * k.crop_y * k.crop_x * t.spp))) != hipSuccess)
         return tvam_hip_fail(e, "hipMalloc (extinction partials)");
-    e = tvam_launch_dsigma(TVAM_MODE_ADJ, p->cone, k, t, pat, idxmap, grad_dose, nullptr, p->dsig_part.get(), g_sigma,
+    e = tvam_launch_dsigma(TVAM_MODE_ADJ, tvam_kind_ray3d(p->kind), k, t, pat, idxmap, grad_dose, nullptr, p->dsig_part.get(), g_sigma,
                            stream);
     return e == hipSuccess ? 0 : tvam_hip_fail(e, "extinction gradient launch");
 }
 
 // Projector derivatives (tvam_dproj.hip).  What both entries refuse, from the descriptor and the
-// plan's flags alone: no device call, nothing allocated.
+// plan's kind alone: no device call, nothing allocated.
 static int dproj_check(const tvam_plan* p, int32_t param, const char* who) {
     const tvam_desc& d = p->desc;
     const char* why = nullptr;
     std::string vial;
-    if (p->refl) why = "a plan with reflected paths (transmission_only = 0)";
-    else if (p->ins) why = "a plan with dielectric occluders (inserts)";
-    else if (p->dbl) why = "a 'double_cylindrical' vial";
-    else if (p->mesh) why = "a 'custom' vial";
-    else if (d.vial_type != TVAM_VIAL_INDEX_MATCHED) {
-        vial = std::string(p->traced ? "a traced '" : "a '") + (d.vial_type == TVAM_VIAL_SQUARE ? "square" : "cylindrical") +
-               "' vial";
+    switch (p->kind) {  // index-matched vials only
+    case K::Reflect: why = "a plan with reflected paths (transmission_only = 0)"; break;
+    case K::Inserts: why = "a plan with dielectric occluders (inserts)"; break;
+    case K::Double: why = "a 'double_cylindrical' vial"; break;
+    case K::Mesh: why = "a 'custom' vial"; break;
+    case K::Traced: case K::Plain: case K::Cone:
+        if (d.vial_type == TVAM_VIAL_INDEX_MATCHED) break;
+        vial = std::string(p->kind == K::Traced ? "a traced '" : "a '") +
+               (d.vial_type == TVAM_VIAL_SQUARE ? "square" : "cylindrical") + "' vial";
         why = vial.c_str();
-    } else if (d.albedo > 0.0f) why = "albedo > 0 (a scattering medium)";
+        break;
+    }
+    if (why) return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string(who) + ": " + why);
+    if (d.albedo > 0.0f) why = "albedo > 0 (a scattering medium)";
     else if (d.sensor_type != TVAM_SENSOR_DDA) why = "the 'ratio' / 'delta' sensors are not differentiated";
     else if (p->surface) why = "a surface-aware (two-channel) film is not differentiated";
     else if (p->k.z0 != 0 || p->k.nz != p->k.res[2]) why = "a film slab is not differentiated (render the whole film)";
@@ -616,9 +636,12 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
                               uint32_t seed, float* rays, void* stream_) {
     if (!p || (!rays && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
     const tvam_desc& d = p->desc;
-    if ((d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CUSTOM &&
-         d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL && !p->traced) ||
-        d.albedo != 0.0f || (d.n_occluder_tris > 0 && !p->ins))
+    bool served = d.albedo == 0.0f && (d.n_occluder_tris == 0 || tvam_kind_inserts(p->kind));  // (the insert walk meets them)
+    switch (p->kind) {
+    case K::Plain: served = served && d.vial_type == TVAM_VIAL_INDEX_MATCHED; break;  // (planar refraction: not these rays)
+    case K::Cone: case K::Traced: case K::Mesh: case K::Double: case K::Inserts: case K::Reflect: break;
+    }
+    if (!served)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_rays: index-matched, 'custom', 'double_cylindrical' and traced glass vial plans without scattering or occluders only");
     return export_rays(p, active_pixels, n_active, spp, seed, rays, nullptr, stream_);
 }
@@ -626,9 +649,12 @@ extern "C" int tvam_plan_rays(tvam_plan* p, const uint32_t* active_pixels, uint6
 extern "C" int tvam_plan_segments(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, uint32_t spp,
                                   uint32_t seed, float* segs, void* stream_) {
     if (!p || (!segs && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (p->refl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with reflected paths (transmission_only = 0) has any number of segments per ray (tvam_plan_insert_segments)");
-    if (p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with dielectric occluders has any number of segments per ray (tvam_plan_insert_segments)");
-    if (!p->dbl) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: 'double_cylindrical' vial plans only");
+    switch (p->kind) {
+    case K::Reflect: return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with reflected paths (transmission_only = 0) has any number of segments per ray (tvam_plan_insert_segments)");
+    case K::Inserts: return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: a plan with dielectric occluders has any number of segments per ray (tvam_plan_insert_segments)");
+    case K::Plain: case K::Cone: case K::Traced: case K::Mesh: return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_segments: 'double_cylindrical' vial plans only");
+    case K::Double: break;
+    }
     if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_segments: segs must be 16-byte aligned");
     return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_, 2);
 }
@@ -637,7 +663,10 @@ extern "C" int tvam_plan_insert_segments(tvam_plan* p, const uint32_t* active_pi
                                          uint32_t seed, int32_t max_segments, float* segs, int32_t* nseg,
                                          void* stream_) {
     if (!p || ((!segs || !nseg) && n_active)) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (!p->ins) return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_insert_segments: plans with dielectric occluders only (tvam_plan_create_inserts; reflected paths: tvam_plan_create_reflect)");
+    switch (p->kind) {
+    case K::Plain: case K::Cone: case K::Traced: case K::Mesh: case K::Double: return tvam_fail(TVAM_ERR_UNSUPPORTED, "tvam_plan_insert_segments: plans with dielectric occluders only (tvam_plan_create_inserts; reflected paths: tvam_plan_create_reflect)");
+    case K::Inserts: case K::Reflect: break;
+    }
     if (max_segments <= 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_insert_segments: max_segments must be positive");
     if (((uintptr_t)segs & 15u) != 0) return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_insert_segments: segs must be 16-byte aligned");
     return export_rays(p, active_pixels, n_active, spp, seed, nullptr, segs, stream_, max_segments, nseg);
@@ -669,8 +698,9 @@ extern "C" int tvam_count_visits(tvam_plan* p, uint32_t spp, uint32_t seed, uint
     if (e != hipSuccess) return tvam_hip_fail(e, "hipMemset");
     TvamTiles t = call_tiles(p, spp, seed);
     if (p->general) {
-        e = p->cone ? launch_ray3d(TVAM_MODE_COUNT, p, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
-                    : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
+        e = tvam_kind_ray3d(p->kind)
+                ? launch_ray3d(TVAM_MODE_COUNT, p, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr)
+                : tvam_launch_general_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, p->counter.get(), nullptr);
     } else if (p->surface) {
         e = tvam_launch_surface_paths(TVAM_MODE_COUNT, k, t, nullptr, nullptr, nullptr, nullptr, nullptr, p->counter.get(),
                                       nullptr);
@@ -697,18 +727,15 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
                           int32_t max_depth, float* radon, void* stream_) {
     if (!p || !radon || n_target_tris < 0 || (n_target_tris > 0 && !target_tris))
         return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (p->refl)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "transmission_only = 0 with filter_radon (the Radon pass's own reflection sampling) is not implemented on the GPU path");
-    if (p->ins)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "dielectric occluders with filter_radon are not implemented on the GPU path");
-    if (p->mesh)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'custom' vial with filter_radon is not implemented on the GPU path");
-    if (p->dbl)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_radon is not implemented on the GPU path");
-    if (p->traced)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a traced 'cylindrical' / 'square' vial with filter_radon is not implemented on the GPU path");
-    if (p->cone)  // the Radon path is a planar ray (tvam_radon_ray)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "the 'telecentric' / 'lens' projectors with filter_radon are not implemented on the GPU path");
+    switch (p->kind) {  // the Radon path is a planar ray (tvam_radon_ray)
+    case K::Reflect: return tvam_fail(TVAM_ERR_UNSUPPORTED, "transmission_only = 0 with filter_radon (the Radon pass's own reflection sampling) is not implemented on the GPU path");
+    case K::Inserts: return tvam_fail(TVAM_ERR_UNSUPPORTED, "dielectric occluders with filter_radon are not implemented on the GPU path");
+    case K::Mesh: return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'custom' vial with filter_radon is not implemented on the GPU path");
+    case K::Double: return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_radon is not implemented on the GPU path");
+    case K::Traced: return tvam_fail(TVAM_ERR_UNSUPPORTED, "a traced 'cylindrical' / 'square' vial with filter_radon is not implemented on the GPU path");
+    case K::Cone: return tvam_fail(TVAM_ERR_UNSUPPORTED, "the 'telecentric' / 'lens' projectors with filter_radon are not implemented on the GPU path");
+    case K::Plain: break;
+    }
     TvamConsts k;
     int rc = call_setup(p, shard_pixels(p), nullptr, spp, k);
     if (rc) return rc;
@@ -733,8 +760,10 @@ extern "C" int tvam_radon(tvam_plan* p, const float* target_tris, int32_t n_targ
 extern "C" int tvam_corner(tvam_plan* p, const uint32_t* active_pixels, uint64_t n_active, float dist, float radius,
                            float* keep, float* hits, void* stream_) {
     if (!p) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: null plan");
-    if (p->dbl)
-        return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_corner is not implemented on the GPU path");
+    switch (p->kind) {
+    case K::Double: return tvam_fail(TVAM_ERR_UNSUPPORTED, "a 'double_cylindrical' vial with filter_corner is not implemented on the GPU path");
+    case K::Plain: case K::Cone: case K::Traced: case K::Mesh: case K::Inserts: case K::Reflect: break;
+    }
     if (!keep) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: null keep");
     if (!(radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: radius must be >= 0");
     if (!std::isfinite(dist)) return tvam_fail(TVAM_ERR_INVALID, "tvam_corner: dist must be finite");
@@ -815,7 +844,7 @@ extern "C" int tvam_plan_fwd_scale(tvam_plan* p, float* scale) {
 // bit 0: planar adjoint (+ ray-driven planar forward unless bit 1), bit 1: voxel-driven planar forward
 // bit 2: 3-D projector rays (telecentric / lens)
 extern "C" int tvam_plan_path(const tvam_plan* p) {
-    return p ? (p->planar ? 1 : 0) | (p->planar_fwd ? 2 : 0) | (p->cone ? 4 : 0) : 0;
+    return p ? (p->planar ? 1 : 0) | (p->planar_fwd ? 2 : 0) | (tvam_kind_ray3d(p->kind) ? 4 : 0) : 0;
 }
 
 extern "C" int tvam_plan_fwd_variant(const tvam_plan* p, int32_t* v) {

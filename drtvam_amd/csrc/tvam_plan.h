@@ -24,30 +24,45 @@ int tvam_upload(TvamDevBuf<T>& b, const std::vector<T>& v) {
 #define TVAM_FROZEN_CAP (1 << 20)
 #define TVAM_STRAY_CAP (1 << 22)  // stray rays per record set (more: the tile kernels use the full row lists)
 
+// The seven sorts of plan: the create entry point a plan came through and, for tvam_plan_create, its
+// projector.  Every kind but Plain runs the 3-D ray kernels (tvam_ray3d.hip).  What a kind's descriptor
+// may ask for is stated once, in validate() (tvam_plan.hip); what a per-call entry refuses of a kind,
+// in that entry's switch (tvam_calls.hip).
+enum class TvamPlanKind {
+    Plain,    // tvam_plan_create, collimated: index-matched, 'cylindrical' or 'square' vial (planar / tile kernels)
+    Cone,     // tvam_plan_create, telecentric / lens: 3-D first segments behind an index-matched vial
+    Traced,   // tvam_plan_create_traced: 'cylindrical' / 'square' vial traced per ray in 3-D (tvam_glass.h)
+    Mesh,     // tvam_plan_create_mesh: 'custom' vial, mesh interfaces traced per ray (tvam_mesh.h)
+    Double,   // tvam_plan_create_double: four tubes traced per ray, two segments (tvam_double.h)
+    Inserts,  // tvam_plan_create_inserts: dielectric occluders walked per ray (tvam_insert.h)
+    Reflect,  // tvam_plan_create_reflect: transmission_only = 0, the insert walk with sampled reflections
+};
+
+// runs the 3-D ray kernels (tvam_ray3d.hip), not the planar, tile and per-path kernels / walks inserts (tvam_insert.h:
+// any number of segments per ray) / has TvamConsts::mesh live (a vial's or the inserts' hierarchy; Double: TvamConsts::dbl)
+inline bool tvam_kind_ray3d(TvamPlanKind kind) { return kind != TvamPlanKind::Plain; }
+inline bool tvam_kind_inserts(TvamPlanKind kind) { return kind == TvamPlanKind::Inserts || kind == TvamPlanKind::Reflect; }
+inline bool tvam_kind_mesh(TvamPlanKind kind) { return kind == TvamPlanKind::Mesh || tvam_kind_inserts(kind); }
+
 struct tvam_plan {
     tvam_desc desc;
-    int device;
-    TvamConsts k;
-    TvamTiles tiles;
-    int32_t ntiles;
-    size_t lds_bytes;
-    int32_t max_rows_per_slice;
+    const TvamPlanKind kind;
+    const int device;
+    TvamConsts k{};
+    TvamTiles tiles{};
+    int32_t ntiles = 0;
+    size_t lds_bytes = 0;
+    int32_t max_rows_per_slice = 0;
     int64_t n_slots_all = 0;  // (angle, column) slots over every tile (tvam_plan_tile_stats)
     int64_t n_main_rows = 0;  // main-row list entries over every slice (0: no main-row lists)
     int64_t n_rows_all = 0;   // row list entries over every slice
-    bool empty;  // max_depth too small for any ray to reach the medium
-    bool cyl;    // refracting (cylindrical / square) vial: per-ray directions and weights
-    bool surface = false;    // surface-aware film (2 channels): per-path kernels cut at the target mesh
-    bool general = false;    // sample_time or a ratio / delta sensor: the general per-path kernel
-    bool cone = false;       // telecentric / lens projector: 3-D first segments (tvam_ray3d.hip); implies general
-    bool mesh = false;       // 'custom' vial: mesh interfaces traced per ray (tvam_mesh.h); implies cone
+    const bool empty;    // (route decisions: the constructor's)  max_depth too small for any ray to reach the medium
+    const bool cyl;      // refracting (cylindrical / square) vial of a Plain plan: per-ray directions and weights
+    const bool surface;  // surface-aware film (2 channels): per-path kernels cut at the target mesh
+    const bool general;  // sample_time, a ratio / delta sensor or a 3-D ray kind: the general per-path kernel
     const float* vols = nullptr;  // caller's compute_volume() output (tvam_plan_set_volumes)
     TvamDevBuf<float> tgt, occ;   // target mesh (surface-aware films) and occluder triangles
-    bool dbl = false;        // 'double_cylindrical' vial: four tubes traced per ray, two segments (tvam_double.h); implies cone
-    bool traced = false;     // 'cylindrical' / 'square' vial traced per ray in 3-D (tvam_plan_create_traced, tvam_glass.h); implies cone
-    bool ins = false;        // dielectric occluders walked per ray (tvam_plan_create_inserts, tvam_insert.h); implies cone
-    bool refl = false;       // transmission_only = 0 (tvam_plan_create_reflect): the insert walk with sampled reflections; implies ins
-    TvamDevBuf<float> ins_eta;      // ... eta of each insert triangle, caller order (the hierarchy: mesh_*)
+    TvamDevBuf<float> ins_eta;      // dielectric occluders: eta of each insert triangle, caller order (the hierarchy: mesh_*)
     TvamDevBuf<float4> mesh_nodes;  // 'custom' vial: the hierarchy over both meshes (TvamMesh)
     TvamDevBuf<float> mesh_tris;
     TvamDevBuf<int32_t> mesh_ids;
@@ -95,10 +110,10 @@ struct tvam_plan {
     TvamDevBuf<unsigned> amax;  // ray-driven forward: per-angle max |pattern|, fixed-point scale
     TvamDevBuf<float> fscale;
     int32_t planar_rz = 4;
-    TvamAdjListBufs adjl;  // planar adjoint: slice-invariant visit lists (tvam_adjlist.hip)
+    TvamAdjListBufs adjl{};  // planar adjoint: slice-invariant visit lists (tvam_adjlist.hip)
     bool adjl_pending = false;  // the lists are to be built by the first adjoint call
     int adjl_parts = 1;
-    TvamBinScratch bins;  // scattering media: brick-binned forward scratch
+    TvamBinScratch bins{};  // scattering media: brick-binned forward scratch
     // sparse scratch (dense crop layout), allocated on first sparse call
     TvamDevBuf<float> dense;
     TvamDevBuf<int32_t> idxmap;
@@ -108,7 +123,7 @@ struct tvam_plan {
     // nothing gives nullptr.  (pl.chord and the visit lists' pl.adjl_* are set by their builders.)
     void bind() {
         k.tgt = tgt.get(), k.occ = occ.get();
-        if (!dbl)  // (k.dbl shares k.mesh's bytes)
+        if (tvam_kind_mesh(kind))  // (else k.dbl may have k.mesh's bytes)
             k.mesh.nodes = mesh_nodes.get(), k.mesh.tris = mesh_tris.get(), k.mesh.ids = mesh_ids.get();
         tiles.cs = cs.get(), tiles.ang = ang.get();
         tiles.slice_off = slice_off.get(), tiles.slice_rows = slice_rows.get();
@@ -122,7 +137,14 @@ struct tvam_plan {
         pl.fwd_part = pl_part.get(), pl.fwd_bin = pl_bin.get();
         pl.fwd_model = pl_fwd_model.get();
     }
-    tvam_plan() = default;
+    // How a plan of (kind, descriptor) is served, decided once.  empty: two glass surfaces + the medium segment (volume.py:179,
+    // :271-272; a double vial's first deposit is at loop iteration 2), index matched: entry bounce + medium segment
+    tvam_plan(TvamPlanKind kind_, const tvam_desc& d, int device_)
+        : desc(d), kind(kind_), device(device_),
+          empty(d.max_depth < (glass(d) || kind_ == TvamPlanKind::Mesh || kind_ == TvamPlanKind::Double ? 3 : 2)),
+          cyl(glass(d) && kind_ == TvamPlanKind::Plain), surface(d.film_channels == 2),
+          general(!surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || tvam_kind_ray3d(kind_))) {}
+    static bool glass(const tvam_desc& d) { return d.vial_type == TVAM_VIAL_CYLINDRICAL || d.vial_type == TVAM_VIAL_SQUARE; }
     tvam_plan(const tvam_plan&) = delete;
     ~tvam_plan() {
         for (auto& r : rs)
@@ -137,9 +159,15 @@ inline bool tvam_cone_binned(const tvam_plan* p) {
     return (fl & TVAM_FLAG_BIN_FIRST) || (!(fl & TVAM_FLAG_SCATTER_ATOMIC) && TVAM_CONE_BINNED_DEFAULT);
 }
 
-// the walk of a 3-D ray plan (p->cone; tvam_ray3d.h)
+// the walk of a 3-D ray plan (tvam_kind_ray3d; tvam_ray3d.h)
 inline int tvam_plan_walk(const tvam_plan* p) {
-    return p->refl ? TVAM_WALK_REFLECT : p->ins ? TVAM_WALK_INSERT : (p->dbl ? TVAM_WALK_DOUBLE : TVAM_WALK_ONE);
+    switch (p->kind) {
+    case TvamPlanKind::Plain: case TvamPlanKind::Cone: case TvamPlanKind::Traced: case TvamPlanKind::Mesh: break;
+    case TvamPlanKind::Double: return TVAM_WALK_DOUBLE;
+    case TvamPlanKind::Inserts: return TVAM_WALK_INSERT;
+    case TvamPlanKind::Reflect: return TVAM_WALK_REFLECT;
+    }
+    return TVAM_WALK_ONE;
 }
 
 // one medium segment as the host segment dumpers write it: o2[3], maxt, d2[3], att

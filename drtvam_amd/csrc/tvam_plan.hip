@@ -82,136 +82,101 @@ extern "C" void tvam_plan_destroy(tvam_plan* p) {
     (void)hipSetDevice(cur);
 }
 
-// traced: the descriptor of tvam_plan_create_traced (a 'cylindrical' / 'square' vial on the 3-D
-// per-ray path, any projector kind)
-// inserts: the descriptor of tvam_plan_create_inserts (dielectric occluders walked per ray)
-// reflect: with inserts, the descriptor of tvam_plan_create_reflect (transmission_only = 0: the same
-// walk with reflection sampled at the dielectric interfaces)
-static int validate(const tvam_desc& d, bool traced = false, bool inserts = false, bool reflect = false) {
+// The kind of a descriptor handed to tvam_plan_create (or tvam_row_slices): no payload beside it.
+static TvamPlanKind desc_kind(const tvam_desc& d) {
+    if (d.vial_type == TVAM_VIAL_CUSTOM) return TvamPlanKind::Mesh;  // (tvam_plan_create refuses these two before it asks)
+    if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) return TvamPlanKind::Double;
+    return d.projector_type != TVAM_PROJECTOR_COLLIMATED ? TvamPlanKind::Cone : TvamPlanKind::Plain;
+}
+
+static bool has_slab(const tvam_desc& d) {
+    return d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2]);
+}
+
+// What the 3-D ray kernels (tvam_ray3d.hip) do not serve, kind by kind: every ray of such a plan is
+// traced in 3-D and runs the per-ray kernels.  A refusal reads subject + limit + tail; the limits that
+// kinds share are stated once, and each kind lists them, with its own, in the order of its refusals.
+static int ray3d_limits(const tvam_desc& d, TvamPlanKind kind) {
+    const char* pn = d.projector_type == TVAM_PROJECTOR_LENS ? "'lens'" : d.projector_type == TVAM_PROJECTOR_TELECENTRIC ? "'telecentric'" : "'collimated'";
+    const std::string projector = std::string("the ") + pn + " projector with ";
+    std::string subject;
+    const char* tail = " is not implemented on the GPU path";
+    switch (kind) {
+    case TvamPlanKind::Plain: return 0;
+    case TvamPlanKind::Cone: subject = projector; break;
+    case TvamPlanKind::Traced: subject = projector, tail = " behind a traced glass vial is not implemented on the GPU path"; break;
+    case TvamPlanKind::Mesh: subject = "a 'custom' vial with "; break;
+    case TvamPlanKind::Double: subject = "a 'double_cylindrical' vial with "; break;
+    case TvamPlanKind::Inserts: subject = "dielectric occluders with ", tail = " are not implemented on the GPU path"; break;
+    case TvamPlanKind::Reflect: subject = "transmission_only = 0 with "; break;
+    }
+    int rc = 0;  // set by the first limit that refuses; each limit returns whether it refused
+    auto no = [&](const std::string& what) { return (rc = tvam_fail(TVAM_ERR_UNSUPPORTED, subject + what + tail)) != 0; };
+    auto invalid = [&](const char* msg) { return (rc = tvam_fail(TVAM_ERR_INVALID, msg)) != 0; };
+    auto lens = [&] {
+        return d.projector_type != TVAM_PROJECTOR_COLLIMATED &&
+               ((!(d.focus_distance > 0.0f) && invalid("focus_distance must be positive")) ||
+                (!(d.aperture_radius >= 0.0f) && invalid("aperture_radius must be >= 0")));
+    };
+    auto occluders = [&] { return d.n_occluder_tris > 0 && no("occluders"); };
+    auto medium_sensor_film = [&] {  // absorbing medium, 'dda' sensor, one-channel film, the whole film
+        return (d.albedo != 0.0f && no("a scattering medium (albedo > 0)")) ||
+               (d.sensor_type == TVAM_SENSOR_RATIO && no("the 'ratio' sensor")) ||
+               (d.sensor_type == TVAM_SENSOR_DELTA && no("the 'delta' sensor")) ||
+               (d.film_channels == 2 && no("a surface-aware film")) || (has_slab(d) && no("film slabs"));
+    };
+    auto refraction_only = [&](const char* where) {
+        return !d.transmission_only && no(std::string("transmission_only = 0 (reflected paths at the ") + where + ")");
+    };
+    auto rr2 = [&] { return d.rr_depth < 2 && no("rr_depth < 2 (Russian roulette before the medium segment)"); };
+    bool refused = false;
+    switch (kind) {  // each kind's limits, its own among them, in the order of its refusals
+    case TvamPlanKind::Plain: break;
+    case TvamPlanKind::Cone:  // index-matched vial (3-D refraction at the glass: the traced entry's, with its own limits)
+        refused = lens() ||
+                  (tvam_plan::glass(d) && (rc = tvam_fail(TVAM_ERR_UNSUPPORTED, subject + "a " + (d.vial_type == TVAM_VIAL_SQUARE ? "'square'" : "'cylindrical'") +
+                                                                      " vial (3-D refraction) needs the traced path: create the plan with tvam_plan_create_traced"))) ||
+                  occluders() || medium_sensor_film();
+        break;
+    case TvamPlanKind::Traced:  // the two analytic surfaces of tvam_glass.h
+        refused = lens() ||
+                  (!(d.vial_r > 0.0f && d.vial_r_ext > d.vial_r && d.vial_ior > 0.0f && d.medium_ior > 0.0f && d.vial_height > 0.0f) &&
+                   invalid("glass vial: need r_ext > r_int > 0 (w_ext > w_int), a positive height and positive IORs")) ||
+                  occluders() || medium_sensor_film() || refraction_only("glass interfaces") || rr2();
+        break;
+    case TvamPlanKind::Mesh:
+        refused = lens() || occluders() || medium_sensor_film() || refraction_only("glass interfaces") || rr2() ||
+                  (!(d.vial_ior > 0.0f && d.medium_ior > 0.0f) && invalid("a 'custom' vial needs positive IORs"));
+        break;
+    case TvamPlanKind::Double:
+        // the last deposit is at loop iteration min(max_depth - 1, 6); Russian roulette acts at
+        // iterations > rr_depth (volume.py:182-185)
+        refused = lens() || occluders() || medium_sensor_film() || refraction_only("glass interfaces") ||
+                  (d.rr_depth < std::min(d.max_depth, 7) - 1 && no("rr_depth < min(max_depth, 7) - 1 (Russian roulette on or before a deposit)")) ||
+                  (!(d.vial_height > 0.0f) && invalid("a 'double_cylindrical' vial needs a positive height"));
+        break;
+    case TvamPlanKind::Inserts:  // black occluders are walked, and Russian roulette is honoured: no limit on either
+    case TvamPlanKind::Reflect:
+        refused = (kind == TvamPlanKind::Reflect && d.transmission_only &&
+                   invalid("tvam_plan_create_reflect: transmission_only = 1 belongs to tvam_plan_create and its siblings")) ||
+                  (d.vial_type == TVAM_VIAL_CUSTOM && no("a 'custom' vial")) ||
+                  (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL && no("a 'double_cylindrical' vial")) || lens() ||
+                  (!(d.vial_height > 0.0f) && invalid("dielectric occluders need a positive vial height")) ||
+                  medium_sensor_film() || (kind == TvamPlanKind::Inserts && refraction_only("interfaces"));
+        break;
+    }
+    return refused ? rc : 0;
+}
+
+// The limits of a descriptor of `kind`, before any device call: the kind's own (ray3d_limits), then every kind's.
+static int validate(const tvam_desc& d, TvamPlanKind kind) {
     if (d.abi_version != TVAM_ABI_VERSION) return tvam_fail(TVAM_ERR_INVALID, "tvam_desc.abi_version mismatch");
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED && d.projector_type != TVAM_PROJECTOR_TELECENTRIC &&
         d.projector_type != TVAM_PROJECTOR_LENS)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'collimated', 'telecentric' and 'lens' projectors are implemented on the GPU path");
-    if (traced && d.vial_type != TVAM_VIAL_CYLINDRICAL && d.vial_type != TVAM_VIAL_SQUARE)
+    if (kind == TvamPlanKind::Traced && d.vial_type != TVAM_VIAL_CYLINDRICAL && d.vial_type != TVAM_VIAL_SQUARE)
         return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_traced: vial_type must be TVAM_VIAL_CYLINDRICAL or TVAM_VIAL_SQUARE (other vials: tvam_plan_create and its siblings)");
-    if (inserts) {
-        // dielectric occluders (tvam_plan_create_inserts): every ray walks the container, the black
-        // occluders and the inserts in 3-D and runs the per-ray kernels of tvam_ray3d.hip, whose
-        // limits these are (Russian roulette is honoured: no limit on rr_depth)
-        auto no = [&](const char* what) {
-            return tvam_fail(TVAM_ERR_UNSUPPORTED,
-                             reflect ? std::string("transmission_only = 0 with ") + what + " is not implemented on the GPU path"
-                                     : std::string("dielectric occluders with ") + what + " are not implemented on the GPU path");
-        };
-        if (reflect && d.transmission_only)
-            return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_reflect: transmission_only = 1 belongs to tvam_plan_create and its siblings");
-        if (d.vial_type == TVAM_VIAL_CUSTOM) return no("a 'custom' vial");
-        if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) return no("a 'double_cylindrical' vial");
-        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
-            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
-            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
-        }
-        if (!(d.vial_height > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "dielectric occluders need a positive vial height");
-        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
-        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
-        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
-        if (d.film_channels == 2) return no("a surface-aware film");
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
-        if (!reflect && !d.transmission_only) return no("transmission_only = 0 (reflected paths at the interfaces)");
-    } else if (d.vial_type == TVAM_VIAL_CUSTOM) {
-        // mesh vial (tvam_plan_create_mesh): every ray is traced in 3-D through the interfaces and
-        // runs the per-ray kernels of tvam_ray3d.hip, whose limits these are
-        auto no = [&](const char* what) {
-            return tvam_fail(TVAM_ERR_UNSUPPORTED,
-                             std::string("a 'custom' vial with ") + what + " is not implemented on the GPU path");
-        };
-        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
-            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
-            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
-        }
-        if (d.n_occluder_tris > 0) return no("occluders");
-        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
-        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
-        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
-        if (d.film_channels == 2) return no("a surface-aware film");
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
-        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
-        if (d.rr_depth < 2) return no("rr_depth < 2 (Russian roulette before the medium segment)");
-        if (!(d.vial_ior > 0.0f && d.medium_ior > 0.0f))
-            return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs positive IORs");
-    } else if (d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL) {
-        // two nested glass tubes (tvam_plan_create_double): every ray is traced in 3-D through the
-        // four interfaces and runs the per-ray kernels of tvam_ray3d.hip, whose limits these are
-        auto no = [&](const char* what) {
-            return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string("a 'double_cylindrical' vial with ") + what +
-                                                  " is not implemented on the GPU path");
-        };
-        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
-            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
-            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
-        }
-        if (d.n_occluder_tris > 0) return no("occluders");
-        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
-        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
-        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
-        if (d.film_channels == 2) return no("a surface-aware film");
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
-        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
-        // the last deposit is at loop iteration min(max_depth - 1, 6); Russian roulette acts at
-        // iterations > rr_depth (volume.py:182-185)
-        if (d.rr_depth < std::min(d.max_depth, 7) - 1)
-            return no("rr_depth < min(max_depth, 7) - 1 (Russian roulette on or before a deposit)");
-        if (!(d.vial_height > 0.0f))
-            return tvam_fail(TVAM_ERR_INVALID, "a 'double_cylindrical' vial needs a positive height");
-    } else if (traced) {
-        // glass tube or cuvette traced per ray (tvam_plan_create_traced): every ray is traced in 3-D
-        // through the two analytic surfaces (tvam_glass.h) and runs the per-ray kernels of
-        // tvam_ray3d.hip, whose limits these are
-        const char* pn = d.projector_type == TVAM_PROJECTOR_LENS          ? "'lens'"
-                         : d.projector_type == TVAM_PROJECTOR_TELECENTRIC ? "'telecentric'"
-                                                                          : "'collimated'";
-        auto no = [&](const char* what) {
-            return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string("the ") + pn + " projector with " + what +
-                                                  " behind a traced glass vial is not implemented on the GPU path");
-        };
-        if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
-            if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
-            if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
-        }
-        if (!(d.vial_r > 0.0f && d.vial_r_ext > d.vial_r && d.vial_ior > 0.0f && d.medium_ior > 0.0f &&
-              d.vial_height > 0.0f))
-            return tvam_fail(TVAM_ERR_INVALID, "glass vial: need r_ext > r_int > 0 (w_ext > w_int), a positive height and positive IORs");
-        if (d.n_occluder_tris > 0) return no("occluders");
-        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
-        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
-        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
-        if (d.film_channels == 2) return no("a surface-aware film");
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
-        if (!d.transmission_only) return no("transmission_only = 0 (reflected paths at the glass interfaces)");
-        if (d.rr_depth < 2) return no("rr_depth < 2 (Russian roulette before the medium segment)");
-    } else if (d.projector_type != TVAM_PROJECTOR_COLLIMATED) {
-        // 3-D projector rays (tvam_ray3d.hip): index-matched vial, absorbing medium, 'dda' sensor,
-        // one-channel film, the whole film
-        const char* pn = d.projector_type == TVAM_PROJECTOR_LENS ? "'lens'" : "'telecentric'";
-        auto no = [&](const char* what) {
-            return tvam_fail(TVAM_ERR_UNSUPPORTED, std::string("the ") + pn + " projector with " + what +
-                                                  " is not implemented on the GPU path");
-        };
-        if (!(d.focus_distance > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "focus_distance must be positive");
-        if (!(d.aperture_radius >= 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "aperture_radius must be >= 0");
-        // (3-D refraction at the glass: the traced entry's, with its own limits)
-        if (d.vial_type == TVAM_VIAL_CYLINDRICAL || d.vial_type == TVAM_VIAL_SQUARE)
-            return tvam_fail(TVAM_ERR_UNSUPPORTED,
-                             std::string("the ") + pn + " projector with a " +
-                                 (d.vial_type == TVAM_VIAL_SQUARE ? "'square'" : "'cylindrical'") +
-                                 " vial (3-D refraction) needs the traced path: create the plan with tvam_plan_create_traced");
-        if (d.n_occluder_tris > 0) return no("occluders");
-        if (d.albedo != 0.0f) return no("a scattering medium (albedo > 0)");
-        if (d.sensor_type == TVAM_SENSOR_RATIO) return no("the 'ratio' sensor");
-        if (d.sensor_type == TVAM_SENSOR_DELTA) return no("the 'delta' sensor");
-        if (d.film_channels == 2) return no("a surface-aware film");
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])) return no("film slabs");
-    }
+    if (const int rc = ray3d_limits(d, kind)) return rc;
     if (d.sensor_type != TVAM_SENSOR_DDA && d.sensor_type != TVAM_SENSOR_RATIO && d.sensor_type != TVAM_SENSOR_DELTA)
         return tvam_fail(TVAM_ERR_INVALID, "unknown sensor type");
     if (d.sensor_type == TVAM_SENSOR_DELTA && d.albedo == 0.0f)  // volume.py:160-161
@@ -220,8 +185,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         return tvam_fail(TVAM_ERR_INVALID, "the 'ratio' sensor needs a positive majorant");
     if (d.sample_time && d.film_channels != 1)
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "sample_time needs a one-channel film");
-    if ((d.sensor_type != TVAM_SENSOR_DDA || d.sample_time) &&
-        (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2])))
+    if ((d.sensor_type != TVAM_SENSOR_DDA || d.sample_time) && has_slab(d))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "sample_time and the ratio / delta sensors need a film without slabs");
     if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && d.vial_type != TVAM_VIAL_CYLINDRICAL &&
         d.vial_type != TVAM_VIAL_SQUARE && d.vial_type != TVAM_VIAL_CUSTOM &&
@@ -229,8 +193,8 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "only the 'index_matched', 'cylindrical', 'square', 'custom' and 'double_cylindrical' containers are implemented on the GPU path");
     // transmission_only = False lets the reference sample reflection as well as refraction at every
     // dielectric interface after the first (volume.py:235-243, radon.py:87-95); the kernels only
-    // refract.  An index-matched vial has no such interface.
-    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !d.transmission_only && !reflect)
+    // refract.  An index-matched vial has no such interface; a Reflect plan's kernels sample both.
+    if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !d.transmission_only && kind != TvamPlanKind::Reflect)
         return tvam_fail(TVAM_ERR_UNSUPPORTED,
                          std::string("transmission_only = 0 behind a ") +
                              (d.vial_type == TVAM_VIAL_SQUARE ? "'square'" : "'cylindrical'") +
@@ -241,20 +205,19 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
     if (d.film_channels == 2) {
         if (d.n_target_tris <= 0 || !d.target_tris)
             return tvam_fail(TVAM_ERR_INVALID, "No target shape found in the scene");  // sensor.py:60-61
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2]))
-            return tvam_fail(TVAM_ERR_UNSUPPORTED, "surface-aware films cannot be split into slabs");
+        if (has_slab(d)) return tvam_fail(TVAM_ERR_UNSUPPORTED, "surface-aware films cannot be split into slabs");
     }
     if (!(d.albedo >= 0.0f && d.albedo <= 1.0f)) return tvam_fail(TVAM_ERR_INVALID, "medium albedo must lie in [0, 1]");
     if (d.albedo != 0.0f) {
         if (!(d.sigma_t > 0.0f)) return tvam_fail(TVAM_ERR_INVALID, "scattering medium: extinction must be positive");
         if (d.phase_type < TVAM_PHASE_ISOTROPIC || d.phase_type > TVAM_PHASE_HG)
             return tvam_fail(TVAM_ERR_UNSUPPORTED, "unknown phase function");
-        if (d.slab_begin != 0 || (d.slab_end >= 0 && d.slab_end != d.film_res[2]))
+        if (has_slab(d))
             return tvam_fail(TVAM_ERR_UNSUPPORTED, "scattered paths leave their slice: film slabs need a non-scattering medium");
     }
     // the medium segment is path vertex 1 (index matched) or 2 (behind two glass
     // surfaces); Russian roulette starts at depth > rr_depth (volume.py:182-185)
-    if (!inserts && d.vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL &&
+    if (!tvam_kind_inserts(kind) && kind != TvamPlanKind::Double &&
         d.rr_depth < (d.vial_type == TVAM_VIAL_INDEX_MATCHED ? 1 : 2))
         return tvam_fail(TVAM_ERR_UNSUPPORTED, "Russian roulette before the medium segment (rr_depth too small) is not implemented");
     if (d.n_patterns <= 0 || d.res_x <= 0 || d.res_y <= 0) return tvam_fail(TVAM_ERR_INVALID, "projector resolution and n_patterns must be positive");
@@ -269,7 +232,7 @@ static int validate(const tvam_desc& d, bool traced = false, bool inserts = fals
     }
     // (a 'custom' vial's surfaces are its meshes: vial_r, vial_r_ext and vial_height are unused; a
     // 'double_cylindrical' vial's radii are tvam_double_vial's)
-    const bool own_surfaces = d.vial_type == TVAM_VIAL_CUSTOM || d.vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL;
+    const bool own_surfaces = kind == TvamPlanKind::Mesh || kind == TvamPlanKind::Double;
     if (!own_surfaces && !(d.vial_r > 0.0f))
         return tvam_fail(TVAM_ERR_INVALID, "vial radius must be positive");
     if (d.vial_type != TVAM_VIAL_INDEX_MATCHED && !own_surfaces &&
@@ -1324,9 +1287,6 @@ static int upload_vial_meshes(tvam_plan* p, const float* outer, int32_t n_outer,
     return 0;
 }
 
-static int plan_create(const tvam_desc& d, const float* outer, int32_t n_outer, const float* inner, int32_t n_inner,
-                       const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced = false,
-                       const tvam_insert* inserts = nullptr, int32_t n_inserts = 0, bool reflect = false);
 // tvam_double.hip
 int tvam_double_validate(const tvam_double_vial* v, float medium_ior);
 TvamDouble tvam_double_consts(const tvam_double_vial& v, float medium_ior);
@@ -1344,193 +1304,49 @@ static int upload_inserts(tvam_plan* p, const tvam_insert* inserts, int32_t n_in
     return tvam_upload(p->ins_eta, tri_eta);
 }
 
-extern "C" int tvam_plan_create_inserts(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
-                                        int device, tvam_plan** out) {
-    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    int rc = validate(*desc, false, true);
-    if (rc) return rc;
-    if ((rc = tvam_inserts_validate(make_consts(*desc, 0, 0), inserts, n_inserts))) return rc;
-    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out, false, inserts, n_inserts);
-}
+// What a create entry point or a host segment dumper was handed beside the descriptor: the kind and its payload.
+struct PlanInputs {
+    TvamPlanKind kind;
+    const float *outer = nullptr, *inner = nullptr;  // Mesh: the two vial meshes
+    int32_t n_outer = 0, n_inner = 0;
+    const tvam_double_vial* dbl = nullptr;  // Double
+    const tvam_insert* inserts = nullptr;   // Inserts, Reflect (which may have none)
+    int32_t n_inserts = 0;
+};
 
-// The host walk of such a plan (tvam_insert.h), ray by ray: no device call.
-extern "C" int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
-                                    const float* o, const float* d, int64_t n_rays, const float* u,
-                                    int32_t max_segments, float* segs, int32_t* nseg) {
-    if (!desc || n_rays < 0 || max_segments < 0 || (n_rays > 0 && (!o || !d || !nseg || (max_segments > 0 && !segs))))
-        return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    int rc = validate(*desc, false, true);
+// The descriptor's limits (validate), then the payload's: no device call.
+static int inputs_validate(const tvam_desc& d, const PlanInputs& in) {
+    int rc = validate(d, in.kind);
     if (rc) return rc;
-    TvamConsts k = make_consts(*desc, 0, 0);
-    if ((rc = tvam_inserts_validate(k, inserts, n_inserts))) return rc;
-    if (desc->n_occluder_tris > 0) {
-        k.occ = desc->occluder_tris;
-        occ_bounds(k, desc->occluder_tris, desc->n_occluder_tris);
-    }
-    std::vector<float> tris, tri_eta;
-    tvam_inserts_flatten(inserts, n_inserts, tris, tri_eta);
-    TvamMeshHost h;
-    tvam_mesh_build(tris.data(), (int32_t)tri_eta.size(), h);
-    TvamInsertScene sc;
-    sc.mesh.nodes = h.nodes.data(), sc.mesh.tris = h.tris.data(), sc.mesh.ids = h.ids.data();
-    sc.mesh.n_nodes = (int32_t)(h.nodes.size() / 2), sc.mesh.n_tris = (int32_t)tri_eta.size(), sc.mesh.n_inner = 0;
-    sc.tri_eta = tri_eta.data();
-    for (int64_t i = 0; i < n_rays; ++i) {
-        TvamInsertWalk w;
-        tvam_insert_start(w, o + 3 * i, d + 3 * i);
-        TvamInsertHostDraws dr{u ? u + 4 * (size_t)k.max_depth * (size_t)i : nullptr};
-        float* row = segs + 8 * (size_t)max_segments * (size_t)i;
-        if (max_segments > 0) std::fill(row, row + 8 * (size_t)max_segments, 0.0f);
-        int32_t s = 0;
-        float o2[3], d2[3], maxt, att;
-        while (tvam_insert_next(k, sc, u != nullptr, dr, w, o2, d2, maxt, att)) {
-            if (s < max_segments) {
-                seg_row(row + 8 * s, o2, d2, maxt, att);
-            }
-            ++s;
-        }
-        nseg[i] = s;
+    switch (in.kind) {
+    case TvamPlanKind::Plain: case TvamPlanKind::Cone: case TvamPlanKind::Traced: break;
+    case TvamPlanKind::Mesh:
+        if ((rc = tvam_mesh_validate("outer", in.outer, in.n_outer)) || (rc = tvam_mesh_validate("inner", in.inner, in.n_inner)))
+            return rc;
+        if ((int64_t)in.n_outer + in.n_inner >= (1 << 27))
+            return tvam_fail(TVAM_ERR_TOO_LARGE, "the vial meshes have too many triangles");
+        break;
+    case TvamPlanKind::Double: return tvam_double_validate(in.dbl, d.medium_ior);
+    case TvamPlanKind::Reflect:  // a glass vial needs no insert; the index-matched tube has no interface of its own and needs one
+        if (in.n_inserts < 0 || (in.n_inserts > 0 && !in.inserts))
+            return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_reflect: inserts is null");
+        if (in.n_inserts == 0 && d.vial_type == TVAM_VIAL_INDEX_MATCHED)
+            return tvam_fail(TVAM_ERR_INVALID, "transmission_only = 0 behind an 'index_matched' vial without inserts has no dielectric interface: create the plan with tvam_plan_create");
+        if (in.n_inserts == 0) break;
+        [[fallthrough]];
+    case TvamPlanKind::Inserts: return tvam_inserts_validate(make_consts(d, 0, 0), in.inserts, in.n_inserts);
     }
     return 0;
 }
 
-// transmission_only = 0: the walk of tvam_plan_create_inserts with reflection sampled against
-// refraction at every dielectric interface after a path's first (tvam_insert_next<true>).  A glass
-// vial needs no insert; the index-matched tube has no interface of its own and needs one.
-static int reflect_validate(const tvam_desc& d, const tvam_insert* inserts, int32_t n_inserts) {
-    int rc = validate(d, false, true, true);
+static int plan_create(const tvam_desc& d_in, const PlanInputs& in, int device, tvam_plan** out) {
+    int rc = inputs_validate(d_in, in);
     if (rc) return rc;
-    if (n_inserts < 0 || (n_inserts > 0 && !inserts))
-        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_reflect: inserts is null");
-    if (n_inserts == 0 && d.vial_type == TVAM_VIAL_INDEX_MATCHED)
-        return tvam_fail(TVAM_ERR_INVALID, "transmission_only = 0 behind an 'index_matched' vial without inserts has no dielectric interface: create the plan with tvam_plan_create");
-    return n_inserts > 0 ? tvam_inserts_validate(make_consts(d, 0, 0), inserts, n_inserts) : 0;
-}
-
-extern "C" int tvam_plan_create_reflect(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
-                                        int device, tvam_plan** out) {
-    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    int rc = reflect_validate(*desc, inserts, n_inserts);
-    if (rc) return rc;
-    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out, false, inserts, n_inserts, true);
-}
-
-// The host walk of such a plan, ray by ray: no device call.  u [n_rays][max_depth][4] is required:
-// a reflecting walk always draws.
-extern "C" int tvam_reflect_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
-                                     const float* o, const float* d, int64_t n_rays, const float* u,
-                                     int32_t max_segments, float* segs, int32_t* nseg) {
-    if (!desc || n_rays < 0 || max_segments < 0 || (n_rays > 0 && (!o || !d || !nseg || (max_segments > 0 && !segs))))
-        return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (n_rays > 0 && !u) return tvam_fail(TVAM_ERR_INVALID, "tvam_reflect_segments: u is required (a reflecting walk always draws)");
-    int rc = reflect_validate(*desc, inserts, n_inserts);
-    if (rc) return rc;
-    TvamConsts k = make_consts(*desc, 0, 0);
-    if (desc->n_occluder_tris > 0) {
-        k.occ = desc->occluder_tris;
-        occ_bounds(k, desc->occluder_tris, desc->n_occluder_tris);
-    }
-    std::vector<float> tris, tri_eta;
-    TvamMeshHost h;
-    TvamInsertScene sc{};
-    if (n_inserts > 0) {
-        tvam_inserts_flatten(inserts, n_inserts, tris, tri_eta);
-        tvam_mesh_build(tris.data(), (int32_t)tri_eta.size(), h);
-        sc.mesh.nodes = h.nodes.data(), sc.mesh.tris = h.tris.data(), sc.mesh.ids = h.ids.data();
-        sc.mesh.n_nodes = (int32_t)(h.nodes.size() / 2), sc.mesh.n_tris = (int32_t)tri_eta.size(), sc.mesh.n_inner = 0;
-        sc.tri_eta = tri_eta.data();
-    }
-    for (int64_t i = 0; i < n_rays; ++i) {
-        TvamInsertWalk w;
-        tvam_insert_start(w, o + 3 * i, d + 3 * i);
-        TvamInsertHostDraws dr{u + 4 * (size_t)k.max_depth * (size_t)i};
-        float* row = segs + 8 * (size_t)max_segments * (size_t)i;
-        if (max_segments > 0) std::fill(row, row + 8 * (size_t)max_segments, 0.0f);
-        int32_t s = 0;
-        float o2[3], d2[3], maxt, att;
-        while (n_inserts > 0 ? tvam_insert_next<true, true>(k, sc, true, dr, w, o2, d2, maxt, att)
-                             : tvam_insert_next<true, false>(k, sc, true, dr, w, o2, d2, maxt, att)) {
-            if (s < max_segments) seg_row(row + 8 * s, o2, d2, maxt, att);
-            ++s;
-        }
-        nseg[i] = s;
-    }
-    return 0;
-}
-
-extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** out) {
-    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_CUSTOM)
-        return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs its meshes: create the plan with tvam_plan_create_mesh");
-    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL)
-        return tvam_fail(TVAM_ERR_INVALID, "a 'double_cylindrical' vial needs its radii and IORs: create the plan with tvam_plan_create_double");
-    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out);
-}
-
-extern "C" int tvam_plan_create_double(const tvam_desc* desc, const tvam_double_vial* vial, int device,
-                                       tvam_plan** out) {
-    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL)
-        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_double: vial_type must be TVAM_VIAL_DOUBLE_CYLINDRICAL");
-    int rc = validate(*desc);
-    if (rc) return rc;
-    if ((rc = tvam_double_validate(vial, desc->medium_ior))) return rc;
-    return plan_create(*desc, nullptr, 0, nullptr, 0, vial, device, out);
-}
-
-extern "C" int tvam_plan_create_traced(const tvam_desc* desc, int device, tvam_plan** out) {
-    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    return plan_create(*desc, nullptr, 0, nullptr, 0, nullptr, device, out, true);
-}
-
-// The host tracer of such a plan (tvam_glass.h), ray by ray: no device call.
-extern "C" int tvam_traced_segments(const tvam_desc* desc, const float* o, const float* d, int64_t n_rays,
-                                    float* segs) {
-    if (!desc || n_rays < 0 || (n_rays > 0 && (!o || !d || !segs))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    if (validate(*desc, true)) return TVAM_ERR_INVALID;  // (the message is the plan entry's)
-    const TvamConsts k = make_consts(*desc, 0, 0);
-    for (int64_t i = 0; i < n_rays; ++i) {
-        float o2[3], d2[3], maxt, att;
-        float* s = segs + 8 * i;
-        if (tvam_segment_traced(k, o + 3 * i, d + 3 * i, o2, d2, maxt, att)) {
-            seg_row(s, o2, d2, maxt, att);
-        } else {
-            for (int j = 0; j < 8; ++j) s[j] = 0.0f;
-        }
-    }
-    return 0;
-}
-
-extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_t n_outer,
-                                     const float* inner_tris, int32_t n_inner, int device, tvam_plan** out) {
-    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type != TVAM_VIAL_CUSTOM)
-        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_mesh: vial_type must be TVAM_VIAL_CUSTOM");
-    int rc = validate(*desc);
-    if (rc) return rc;
-    if ((rc = tvam_mesh_validate("outer", outer_tris, n_outer)) || (rc = tvam_mesh_validate("inner", inner_tris, n_inner)))
-        return rc;
-    if ((int64_t)n_outer + n_inner >= (1 << 27))
-        return tvam_fail(TVAM_ERR_TOO_LARGE, "the vial meshes have too many triangles");
-    return plan_create(*desc, outer_tris, n_outer, inner_tris, n_inner, nullptr, device, out);
-}
-
-static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_outer, const float* inner,
-                       int32_t n_inner, const tvam_double_vial* dbl, int device, tvam_plan** out, bool traced,
-                       const tvam_insert* inserts, int32_t n_inserts, bool reflect) {
     tvam_desc d = d_in;
-    if (dbl) {  // the host tables (tiles, slots) are sized by the medium's tube and the outermost one
-        d.vial_r = dbl->r_int_outer;
-        d.vial_r_ext = dbl->r_ext_outer;
+    if (in.dbl) {  // the host tables (tiles, slots) are sized by the medium's tube and the outermost one
+        d.vial_r = in.dbl->r_int_outer;
+        d.vial_r_ext = in.dbl->r_ext_outer;
     }
-    int rc = validate(d, traced, inserts != nullptr || reflect, reflect);
-    if (rc) return rc;
     int a0 = d.angle_begin, a1 = d.angle_end < 0 ? d.n_patterns : d.angle_end;
     if (a0 < 0 || a1 > d.n_patterns || a0 > a1) return tvam_fail(TVAM_ERR_INVALID, "invalid angle shard");
 
@@ -1540,35 +1356,13 @@ static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_oute
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return tvam_hip_fail(e, "hipSetDevice");
 
-    std::unique_ptr<tvam_plan> p(new tvam_plan());  // (an error exit destroys it on `device`)
-    p->desc = d;
-    p->device = device;
+    std::unique_ptr<tvam_plan> p(new tvam_plan(in.kind, d, device));  // (an error exit destroys it on `device`)
     p->k = make_consts(d, a0, a1);
-    p->cyl = d.vial_type == TVAM_VIAL_CYLINDRICAL || d.vial_type == TVAM_VIAL_SQUARE;
-    // index matched: entry bounce + medium segment; glass vials: two glass
-    // surfaces + medium segment (volume.py:179, :271-272)
-    p->empty = d.max_depth < (p->cyl ? 3 : 2);
-    p->surface = d.film_channels == 2;
-    p->mesh = d.vial_type == TVAM_VIAL_CUSTOM;
-    if (p->mesh) p->empty = d.max_depth < 3;  // two glass surfaces + the medium segment, like the glass vials
-    p->dbl = dbl != nullptr;
-    if (p->dbl) {
-        p->empty = d.max_depth < 3;  // the first deposit is at loop iteration 2
-        p->k.dbl = tvam_double_consts(*dbl, d.medium_ior);
-    }
-    p->ins = inserts != nullptr || reflect;  // (a reflecting plan runs the insert walk, with or without inserts)
-    p->refl = reflect;
-    if (p->ins) {  // a glass vial under the inserts is a traced one (the planar tables are not this path's)
-        traced = p->cyl;
-        p->empty = d.max_depth < (p->cyl ? 3 : 2);
-    }
-    p->traced = traced;
-    if (traced) p->cyl = false;  // (the planar tables and ray records of a refracting vial are not this path's)
-    p->cone = d.projector_type != TVAM_PROJECTOR_COLLIMATED || p->mesh || p->dbl || traced || p->ins;
-    p->general = !p->surface && (d.sample_time || d.sensor_type != TVAM_SENSOR_DDA || p->cone);
+    if (in.dbl) p->k.dbl = tvam_double_consts(*in.dbl, d.medium_ior);
     if ((rc = upload_meshes(p.get())) || (rc = tile_geometry(p.get()))) return rc;
-    if (p->mesh && (rc = upload_vial_meshes(p.get(), outer, n_outer, inner, n_inner))) return rc;
-    if (p->ins && n_inserts > 0 && (rc = upload_inserts(p.get(), inserts, n_inserts))) return rc;
+    if (in.kind == TvamPlanKind::Mesh && (rc = upload_vial_meshes(p.get(), in.outer, in.n_outer, in.inner, in.n_inner)))
+        return rc;
+    if (in.n_inserts > 0 && (rc = upload_inserts(p.get(), in.inserts, in.n_inserts))) return rc;
 
     std::vector<float2> cs;
     std::vector<float4> ang;
@@ -1601,6 +1395,153 @@ static int plan_create(const tvam_desc& d_in, const float* outer, int32_t n_oute
             return tvam_hip_fail(e, "hipEventCreate");
     if (!p->surface && !p->general && (rc = planar_setup(p.get(), cs))) return rc;
     *out = p.release();
+    return 0;
+}
+
+extern "C" int tvam_plan_create(const tvam_desc* desc, int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_CUSTOM)
+        return tvam_fail(TVAM_ERR_INVALID, "a 'custom' vial needs its meshes: create the plan with tvam_plan_create_mesh");
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type == TVAM_VIAL_DOUBLE_CYLINDRICAL)
+        return tvam_fail(TVAM_ERR_INVALID, "a 'double_cylindrical' vial needs its radii and IORs: create the plan with tvam_plan_create_double");
+    return plan_create(*desc, PlanInputs{desc_kind(*desc)}, device, out);
+}
+
+extern "C" int tvam_plan_create_traced(const tvam_desc* desc, int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    return plan_create(*desc, PlanInputs{TvamPlanKind::Traced}, device, out);
+}
+
+extern "C" int tvam_plan_create_mesh(const tvam_desc* desc, const float* outer_tris, int32_t n_outer,
+                                     const float* inner_tris, int32_t n_inner, int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type != TVAM_VIAL_CUSTOM)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_mesh: vial_type must be TVAM_VIAL_CUSTOM");
+    PlanInputs in{TvamPlanKind::Mesh};
+    in.outer = outer_tris, in.n_outer = n_outer, in.inner = inner_tris, in.n_inner = n_inner;
+    return plan_create(*desc, in, device, out);
+}
+
+extern "C" int tvam_plan_create_double(const tvam_desc* desc, const tvam_double_vial* vial, int device,
+                                       tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (desc->abi_version == TVAM_ABI_VERSION && desc->vial_type != TVAM_VIAL_DOUBLE_CYLINDRICAL)
+        return tvam_fail(TVAM_ERR_INVALID, "tvam_plan_create_double: vial_type must be TVAM_VIAL_DOUBLE_CYLINDRICAL");
+    PlanInputs in{TvamPlanKind::Double};
+    in.dbl = vial;
+    return plan_create(*desc, in, device, out);
+}
+
+// Inserts: dielectric occluders walked per ray.  Reflect (transmission_only = 0): the same walk with reflection
+// sampled against refraction at every dielectric interface after a path's first (tvam_insert_next<true>).
+static PlanInputs insert_inputs(TvamPlanKind kind, const tvam_insert* inserts, int32_t n_inserts) {
+    PlanInputs in{kind};
+    in.inserts = inserts, in.n_inserts = n_inserts;
+    return in;
+}
+
+extern "C" int tvam_plan_create_inserts(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                        int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    return plan_create(*desc, insert_inputs(TvamPlanKind::Inserts, inserts, n_inserts), device, out);
+}
+
+extern "C" int tvam_plan_create_reflect(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                        int device, tvam_plan** out) {
+    if (!desc || !out) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    *out = nullptr;
+    return plan_create(*desc, insert_inputs(TvamPlanKind::Reflect, inserts, n_inserts), device, out);
+}
+
+// The host tracer of a Traced plan (tvam_glass.h), ray by ray: no device call.
+extern "C" int tvam_traced_segments(const tvam_desc* desc, const float* o, const float* d, int64_t n_rays,
+                                    float* segs) {
+    if (!desc || n_rays < 0 || (n_rays > 0 && (!o || !d || !segs))) return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (validate(*desc, TvamPlanKind::Traced)) return TVAM_ERR_INVALID;  // (the message is the plan entry's)
+    const TvamConsts k = make_consts(*desc, 0, 0);
+    for (int64_t i = 0; i < n_rays; ++i) {
+        float o2[3], d2[3], maxt, att;
+        float* s = segs + 8 * i;
+        if (tvam_segment_traced(k, o + 3 * i, d + 3 * i, o2, d2, maxt, att)) {
+            seg_row(s, o2, d2, maxt, att);
+        } else {
+            for (int j = 0; j < 8; ++j) s[j] = 0.0f;
+        }
+    }
+    return 0;
+}
+
+// The host walk of an Inserts or Reflect plan (tvam_insert.h), ray by ray: no device call.  Its scene: the descriptor's
+// constants with the caller's occluder triangles, the inserts' flat tables and their hierarchy (none: an empty scene).
+namespace {
+struct HostInsertScene {
+    TvamConsts k;
+    std::vector<float> tris, tri_eta;
+    TvamMeshHost mesh;
+    TvamInsertScene view{};
+    HostInsertScene(const tvam_desc& d, const tvam_insert* inserts, int32_t n_inserts) : k(make_consts(d, 0, 0)) {
+        if (d.n_occluder_tris > 0) {
+            k.occ = d.occluder_tris;
+            occ_bounds(k, d.occluder_tris, d.n_occluder_tris);
+        }
+        if (n_inserts <= 0) return;
+        tvam_inserts_flatten(inserts, n_inserts, tris, tri_eta);
+        tvam_mesh_build(tris.data(), (int32_t)tri_eta.size(), mesh);
+        view.mesh.nodes = mesh.nodes.data(), view.mesh.tris = mesh.tris.data(), view.mesh.ids = mesh.ids.data();
+        view.mesh.n_nodes = (int32_t)(mesh.nodes.size() / 2), view.mesh.n_tris = (int32_t)tri_eta.size(), view.mesh.n_inner = 0;
+        view.tri_eta = tri_eta.data();
+    }
+};
+
+// u [n_rays][max_depth][4]: each loop iteration's draws (null: none, Russian roulette never acts)
+template <bool REFLECT, bool MESHES>
+void host_walk(const HostInsertScene& sc, const float* o, const float* d, int64_t n_rays, const float* u,
+               int32_t max_segments, float* segs, int32_t* nseg) {
+    for (int64_t i = 0; i < n_rays; ++i) {
+        TvamInsertWalk w;
+        tvam_insert_start(w, o + 3 * i, d + 3 * i);
+        TvamInsertHostDraws dr{u ? u + 4 * (size_t)sc.k.max_depth * (size_t)i : nullptr};
+        float* row = segs + 8 * (size_t)max_segments * (size_t)i;
+        if (max_segments > 0) std::fill(row, row + 8 * (size_t)max_segments, 0.0f);
+        int32_t s = 0;
+        float o2[3], d2[3], maxt, att;
+        while (tvam_insert_next<REFLECT, MESHES>(sc.k, sc.view, u != nullptr, dr, w, o2, d2, maxt, att)) {
+            if (s < max_segments) seg_row(row + 8 * s, o2, d2, maxt, att);
+            ++s;
+        }
+        nseg[i] = s;
+    }
+}
+}  // namespace
+
+extern "C" int tvam_insert_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                    const float* o, const float* d, int64_t n_rays, const float* u,
+                                    int32_t max_segments, float* segs, int32_t* nseg) {
+    if (!desc || n_rays < 0 || max_segments < 0 || (n_rays > 0 && (!o || !d || !nseg || (max_segments > 0 && !segs))))
+        return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (const int rc = inputs_validate(*desc, insert_inputs(TvamPlanKind::Inserts, inserts, n_inserts))) return rc;
+    host_walk<false, true>(HostInsertScene(*desc, inserts, n_inserts), o, d, n_rays, u, max_segments, segs, nseg);
+    return 0;
+}
+
+// u is required: a reflecting walk always draws.
+extern "C" int tvam_reflect_segments(const tvam_desc* desc, const tvam_insert* inserts, int32_t n_inserts,
+                                     const float* o, const float* d, int64_t n_rays, const float* u,
+                                     int32_t max_segments, float* segs, int32_t* nseg) {
+    if (!desc || n_rays < 0 || max_segments < 0 || (n_rays > 0 && (!o || !d || !nseg || (max_segments > 0 && !segs))))
+        return tvam_fail(TVAM_ERR_INVALID, "null argument");
+    if (n_rays > 0 && !u) return tvam_fail(TVAM_ERR_INVALID, "tvam_reflect_segments: u is required (a reflecting walk always draws)");
+    if (const int rc = inputs_validate(*desc, insert_inputs(TvamPlanKind::Reflect, inserts, n_inserts))) return rc;
+    const HostInsertScene sc(*desc, inserts, n_inserts);
+    if (n_inserts > 0)
+        host_walk<true, true>(sc, o, d, n_rays, u, max_segments, segs, nseg);
+    else
+        host_walk<true, false>(sc, o, d, n_rays, u, max_segments, segs, nseg);
     return 0;
 }
 
@@ -1637,8 +1578,9 @@ extern "C" int tvam_plan_kernel_time(tvam_plan* p, int32_t enable, double* total
         // voxel-driven planar forward where it serves, else the per-ray tile forward
         // (telecentric / lens: the brick march of the binned forward, else the per-ray atomic forward)
         // (dielectric occluders: the per-ray atomic forward alone)
-        g_kt.kind = p->cone ? (tvam_cone_binned(p) && !p->ins ? TVAM_KT_BRICK : TVAM_KT_CONE)
-                            : (p->desc.albedo != 0.0f ? TVAM_KT_BRICK : (p->planar_fwd ? TVAM_KT_PLANAR : TVAM_KT_TILE));
+        g_kt.kind = tvam_kind_ray3d(p->kind)
+                        ? (tvam_cone_binned(p) && !tvam_kind_inserts(p->kind) ? TVAM_KT_BRICK : TVAM_KT_CONE)
+                        : (p->desc.albedo != 0.0f ? TVAM_KT_BRICK : (p->planar_fwd ? TVAM_KT_PLANAR : TVAM_KT_TILE));
         g_kt.on = true;
     }
     return 0;
@@ -1646,7 +1588,7 @@ extern "C" int tvam_plan_kernel_time(tvam_plan* p, int32_t enable, double* total
 
 extern "C" int tvam_row_slices(const tvam_desc* desc, int32_t* slice_of_row) {
     if (!desc || !slice_of_row) return tvam_fail(TVAM_ERR_INVALID, "null argument");
-    int rc = validate(*desc);
+    int rc = validate(*desc, desc_kind(*desc));
     if (rc) return rc;
     const tvam_desc& d = *desc;
     if (d.projector_type != TVAM_PROJECTOR_COLLIMATED)  // 3-D rays cross slices: no row <-> slice map
